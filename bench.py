@@ -7,6 +7,14 @@ synthetic MLM data, bf16, random-init weights (BASELINE.json configs).
   python bench.py --gpus N --steps K --warmup W
       [--config bert_dp|bert_pp|bert_zero|resnet_tp|gpt2_xl|moe|moe_pp]
       [--pp S] [--micro-batch M] [--batch B] [--zero v0|v1]
+      [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON
+result line; it measures nothing else.  --full is reserved for extra
+measurements and checks (none today: it runs the same steps).  Weights
+and data are seeded, so two runs with the same arguments see identical
+inputs; --dump-outputs DIR writes what the last timed step returned,
+the loss, as DIR/loss.npy in float32.
 
 For N>1 the driver launches this under torch.distributed.run with one rank
 per GPU (RCCL over xGMI); ranks read RANK/LOCAL_RANK/WORLD_SIZE from env.
@@ -45,6 +53,11 @@ def parse_args():
     p.add_argument("--device", default=None)
     p.add_argument("--dropout", type=float, default=0.0,
                    help="attention dropout (runs in the native kernels)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's outputs as DIR/*.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extra measurements and checks "
+                        "(none today)")
     return p.parse_args()
 
 
@@ -320,6 +333,21 @@ def _enable_tunableop():
         os.environ.setdefault("PYTORCH_TUNABLEOP_VERBOSE", "0")
 
 
+SEED = 20240611   # weights; the data batches carry seeds of their own
+
+
+def dump_outputs(out_dir, loss, rank, world):
+    """Write what train_step returned in the last timed step: the local
+    mean loss, as float32 (loss.npy; loss_rank<r>.npy when world > 1)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if loss is None:   # pipelines: only the last stage has a loss
+        return
+    name = "loss.npy" if world == 1 else "loss_rank{}.npy".format(rank)
+    np.save(os.path.join(out_dir, name),
+            loss.detach().float().reshape(-1).cpu().numpy())
+
+
 def main():
     args = parse_args()
     _enable_tunableop()
@@ -329,6 +357,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     on_gpu = torch.cuda.is_available() if args.device != "cpu" else False
     dtype = torch.bfloat16 if on_gpu else torch.float32
+    # same arguments -> same initial weights (per rank, as unseeded ranks
+    # drew independently before)
+    torch.manual_seed(SEED + rank)
 
     engine, (inputs, targets), samples_per_step, meta = \
         BUILDERS[args.config](args, epl, world, on_gpu, dtype)
@@ -345,10 +376,14 @@ def main():
         engine.train_step(inputs, targets)
     barrier()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        engine.train_step(inputs, targets)
+        loss = engine.train_step(inputs, targets)
     barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, rank, world)
 
     # MAX over ranks
     if dist.is_initialized():
