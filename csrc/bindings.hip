@@ -45,6 +45,7 @@ void epl_colsum(void*, const void*, float*, int64_t, int64_t, int64_t,
                 bool, hipStream_t);
 void run_mfma_probe(const unsigned short*, const unsigned short*, float*,
                     hipStream_t);
+void run_tr_read_probe(short*, short*, int, hipStream_t);
 void epl_moe_dispatch_fwd(void*, const void*, const int64_t*,
                           const int64_t*, const int64_t*, int64_t, int64_t,
                           int64_t, hipStream_t);
@@ -372,6 +373,21 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
                (float)inv_keep, q.size(3), dlse_ptr, cur_stream());
 }
 
+// out_gather / out_tr: int16 [4 * head_dim/32, 64, 8] (fragment, lane,
+// element) — see tr_read_probe_kernel
+void tr_read_probe(at::Tensor out_gather, at::Tensor out_tr,
+                   int64_t head_dim) {
+  TORCH_CHECK(head_dim == 64 || head_dim == 128, "head_dim must be 64|128");
+  check(out_gather, at::kShort, "out_gather");
+  check(out_tr, at::kShort, "out_tr");
+  const int64_t n = 4 * (head_dim / 32) * 64 * 8;
+  TORCH_CHECK(out_gather.numel() == n && out_tr.numel() == n,
+              "probe outputs must hold ", n, " elements");
+  run_tr_read_probe(reinterpret_cast<short*>(out_gather.data_ptr()),
+                    reinterpret_cast<short*>(out_tr.data_ptr()),
+                    (int)head_dim, cur_stream());
+}
+
 void mfma_probe(at::Tensor A, at::Tensor B, at::Tensor D) {
   check(A, at::kBFloat16, "A");
   check(B, at::kBFloat16, "B");
@@ -484,6 +500,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bf16_to_f32", &bf16_to_f32);
   m.def("sqnorm", &sqnorm);
   m.def("mfma_probe", &mfma_probe);
+  m.def("tr_read_probe", &tr_read_probe);
   m.def("moe_dispatch_fwd", &moe_dispatch_fwd);
   m.def("moe_dispatch_bwd", &moe_dispatch_bwd);
   m.def("moe_combine_fwd", &moe_combine_fwd);

@@ -1,7 +1,9 @@
-// Hand-written CDNA4 (gfx950) flash attention, head_dim = 64, bf16.
+// Hand-written CDNA4 (gfx950) flash attention, head_dim 64 and 128,
+// bf16, causal or not, optional in-kernel dropout.
 //
-// Replaces the AOTriton SDPA kernels on the BERT/GPT hot path (measured
-// ~315 TF fwd / ~183 TF bwd on MI355X at our shapes; see profiles/).
+// Replaces the AOTriton SDPA kernels on the BERT/GPT hot path (BERT-Large
+// shape b128 s512 h16 d64 on MI355X: fwd ~340 us, bwd ~1190 us for the
+// three kernels; profiles/attn_bwd_tiles_ab.txt).
 //
 // Forward structure (cdna_hip_programming.md section B recipe, adapted to
 // one 32-row q-block per wave, 32-key kv tiles, head_dim 64):
@@ -17,18 +19,36 @@
 //    from global (L2-resident tiles); V^T fragments gather columns (L2).
 // Saves per-row LSE (m + log l) for the backward.
 //
-// Backward: two kernels (kv-parallel for dK/dV, q-parallel for dQ), each
-// lane owning its output row — no atomics.  D_i = rowsum(dO*O) is
-// precomputed by a small kernel.  All kernels take (batch, head, seq)
-// strides so the qkv-unbind views are consumed without copies.
+// Backward: three kernels launched dV -> dQ -> dK (kv-parallel for dV
+// and dK, q-parallel for dQ), each lane owning its output row — no
+// atomics.  The dQ kernel computes D_i = rowsum(dO*O) from the rows it
+// already loads and publishes it for the dK kernel.  64-row q/dO (or
+// K/V) chunks are staged in one LDS image per tile that is read by rows
+// (ds_read_b128) for S and dP and by columns (ds_read_b64_tr_b16) for
+// dV^T, dK^T and dQ; the dV/dK kernels stage the chunk's -lse/scale and
+// -delta next to it and start the S and dP chains from them.
+// EPL_ATTN_BWD_TILES=legacy selects the previous tile bodies (2-byte
+// LDS gathers, row constants from global memory) for a same-process
+// A/B.  A combined dK+dV kernel (d64, non-causal) stays behind
+// EPL_ATTN_BWD_SPLIT=0.  All kernels take (batch, head, seq) strides so
+// the qkv-unbind views are consumed without copies.
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+
+#include "attn_lds_image.h"
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using bf16x4 = __attribute__((ext_vector_type(4))) short;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using i32x2 = __attribute__((ext_vector_type(2))) int;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using bf16v2 = __attribute__((ext_vector_type(2))) __bf16;
 
 #define DEVI __device__ __forceinline__
 
@@ -56,13 +76,24 @@ DEVI int crow(int r, int hi) {
   return (r & 3) + 8 * (r >> 2) + 4 * hi;
 }
 
+// two floats -> packed bf16 pair, round-to-nearest-even, in one
+// v_cvt_pk_bf16_f32 (bit-identical to pack2 for finite values)
+DEVI unsigned int cvt_pk_bf16(float a, float b) {
+  f32x2 f = {a, b};
+  return __builtin_bit_cast(unsigned int,
+                            __builtin_convertvector(f, bf16v2));
+}
+
 // assemble the P^T mfma operand from 8 f32 scores (p[0..7] at rows
-// crow(0..7, hi)): returns bf16x8 with element j = P at kv = hi*8+j
+// crow(0..7, hi)): returns bf16x8 with element j = P at kv = hi*8+j.
+// HW selects the packed hardware convert; the legacy backward tiles keep
+// the software rounding so the A/B switch compares the parent's bodies.
+template <bool HW = false>
 DEVI bf16x8 assemble_pfrag(const float* p) {
-  unsigned int c0 = pack2(p[0], p[1]);
-  unsigned int c1 = pack2(p[2], p[3]);
-  unsigned int c2 = pack2(p[4], p[5]);
-  unsigned int c3 = pack2(p[6], p[7]);
+  unsigned int c0 = HW ? cvt_pk_bf16(p[0], p[1]) : pack2(p[0], p[1]);
+  unsigned int c1 = HW ? cvt_pk_bf16(p[2], p[3]) : pack2(p[2], p[3]);
+  unsigned int c2 = HW ? cvt_pk_bf16(p[4], p[5]) : pack2(p[4], p[5]);
+  unsigned int c3 = HW ? cvt_pk_bf16(p[6], p[7]) : pack2(p[6], p[7]);
   i32x2 r = __builtin_amdgcn_permlane32_swap((int)c0, (int)c2, false, false);
   i32x2 s = __builtin_amdgcn_permlane32_swap((int)c1, (int)c3, false, false);
   union { unsigned int d[4]; bf16x8 v; } out;
@@ -71,6 +102,61 @@ DEVI bf16x8 assemble_pfrag(const float* p) {
   out.d[2] = (unsigned int)r[1];
   out.d[3] = (unsigned int)s[1];
   return out.v;
+}
+
+// dual-use LDS image (row reads + transposed reads) of the backward's
+// new tile bodies: layout and fragment readers in attn_lds_image.h
+using attn_img::img_off;
+using attn_img::img_pitch;
+using attn_img::tr_frag;
+
+// staging-store address of columns col..col+7 (col % 8 == 0) of a row:
+// the legacy tiles' padded rows, or the dual-use image of the new ones
+template <bool TR, int D>
+DEVI short* img_at(short (&img)[64][TR ? img_pitch<D>() : D + 8], int row,
+                   int col) {
+  return TR ? &img[0][0] + img_off<D>(row, col >> 3) : &img[row][col];
+}
+
+// the 16 per-row constants of one lane's accumulator rows
+// (crow(r, hi) = four consecutive rows per r>>2): four ds_read_b128,
+// delivered as an accumulator so an MFMA chain can start from them
+DEVI f32x16 load_rowconst(const float* c32, int hi) {
+  f32x16 out;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(c32 + 8 * g + 4 * hi);
+    out[4 * g + 0] = v[0];
+    out[4 * g + 1] = v[1];
+    out[4 * g + 2] = v[2];
+    out[4 * g + 3] = v[3];
+  }
+  return out;
+}
+
+// MASKED tiles: the legacy test (qg >= seq || (causal && mykv > qg) ||
+// mykv >= seq) for tile row c = crow(r, hi), qg = q0 + c, as two 32-bit
+// bounds: masked <=> c < lo || c >= hi_
+struct RowMask {
+  int lo, hi_;
+  DEVI RowMask(int64_t q0, int64_t seq, int64_t mykv, int causal) {
+    const int64_t rows = seq - q0;
+    hi_ = mykv >= seq ? 0 : (rows < 32 ? (int)rows : 32);
+    const int64_t d = mykv - q0;
+    lo = (causal && d > 0) ? (d < 32 ? (int)d : 32) : 0;
+  }
+  DEVI bool masked(int c) const { return c < lo || c >= hi_; }
+};
+
+// epilogue: one lane's 16 accumulator rows of a 32-wide column block,
+// rows crow(r, hi) -> four packed 8-byte stores
+DEVI void store_acc_bf16(short* p, const f32x16& acc, int hi) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    u32x2 v = {cvt_pk_bf16(acc[4 * g], acc[4 * g + 1]),
+               cvt_pk_bf16(acc[4 * g + 2], acc[4 * g + 3])};
+    *reinterpret_cast<u32x2*>(p + 8 * g + 4 * hi) = v;
+  }
 }
 
 // ----------------------------------------------------------------------------
@@ -191,8 +277,8 @@ DEVI void fwd_tile(const short (&ldsK)[64][D + 8],
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       ot[j][r] *= alpha;
-  bf16x8 pf0 = assemble_pfrag(&s[0]);
-  bf16x8 pf1 = assemble_pfrag(&s[8]);
+  bf16x8 pf0 = assemble_pfrag<true>(&s[0]);
+  bf16x8 pf1 = assemble_pfrag<true>(&s[8]);
 #pragma unroll
   for (int kc = 0; kc < 2; ++kc) {
     bf16x8 pf = kc == 0 ? pf0 : pf1;
@@ -332,9 +418,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
   short* op = out + (bh / heads) * o_sb + (bh % heads) * o_sh + myq * o_ss;
 #pragma unroll
   for (int j = 0; j < D / 32; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      op[j * 32 + crow(r, hi)] = (short)f2bf(ot[j][r] * inv_l);
+    store_acc_bf16(op + j * 32, ot[j] * inv_l, hi);
   if (hi == 0) lse[bh * seq + myq] = m + __logf(l);
 }
 
@@ -623,8 +707,130 @@ DEVI void dk_tile(const short (&ldsQ)[64][D + 8],
   }
 }
 
-template <bool DROP, bool DBUF, int D>
-__global__ __launch_bounds__(256, D == 64 ? (DBUF ? 3 : 4) : 2)
+// ----------------------------------------------------------------------------
+// New tile bodies (default; EPL_ATTN_BWD_TILES=legacy selects the ones
+// above).  Same products; what changes is how the operands arrive:
+//  * Q/dO live in the dual-use image (img_off) and the transposed
+//    fragments come from two ds_read_b64_tr_b16 instead of eight 2-byte
+//    reads;
+//  * lse (and delta) of the chunk's 64 rows are staged in LDS with the
+//    chunk and read as four ds_read_b128 instead of 16 global loads;
+//  * bf16 rounding is v_cvt_pk_bf16_f32.
+// lseL/dltL point at the 32 row constants of this sub-tile, staged as
+// -lse/scale and -delta so the S and dP chains start from them and
+// P = exp2(scale*log2(e) * S') needs no subtraction; rows past seq hold
+// the clamped row's value, as the legacy bodies read it.
+// ----------------------------------------------------------------------------
+template <bool MASKED, bool DROP, int D>
+DEVI void dv_tile_tr(const short* imgQ, const short* imgDO,
+                     const float* lseL, int sub, int64_t q0, int64_t seq,
+                     int64_t mykv, float scale, int causal,
+                     const bf16x8 (&kfrag)[D / 16], f32x16 (&dvt)[D / 32],
+                     int lkv, int hi, const unsigned int* maskrow,
+                     int64_t mask_w, float inv_keep) {
+  // row constants as the initial accumulator: S' = Q K^T - lse/scale
+  f32x16 st = load_rowconst(lseL, hi);
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) {
+    bf16x8 qf = *reinterpret_cast<const bf16x8*>(
+        imgQ + img_off<D>(sub + lkv, 2 * c + hi));
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfrag[c], st, 0, 0, 0);
+  }
+  const float c2 = scale * 1.44269504088896341f;   // P = exp2(c2 * S')
+  const RowMask rm(q0, seq, mykv, causal);
+  float p[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if (MASKED)
+      p[r] = rm.masked(crow(r, hi)) ? 0.f
+                                    : __builtin_amdgcn_exp2f(st[r] * c2);
+    else
+      p[r] = __builtin_amdgcn_exp2f(st[r] * c2);
+    if (DROP) {
+      const int64_t qg = q0 + crow(r, hi);
+      const int64_t qgc = qg < seq ? qg : seq - 1;
+      const int64_t kvc = mykv < seq ? mykv : seq - 1;
+      const unsigned int w = maskrow[qgc * mask_w + (kvc >> 5)];
+      p[r] *= ((w >> (kvc & 31)) & 1u) ? inv_keep : 0.f;
+    }
+  }
+  bf16x8 pb0 = assemble_pfrag<true>(&p[0]);
+  bf16x8 pb1 = assemble_pfrag<true>(&p[8]);
+  const int lane = hi * 32 + lkv;
+#pragma unroll
+  for (int qc = 0; qc < 2; ++qc) {
+    bf16x8 pb = qc == 0 ? pb0 : pb1;
+#pragma unroll
+    for (int dj = 0; dj < D / 32; ++dj) {
+      bf16x8 dot = tr_frag<D>(imgDO, sub + qc * 16, dj, lane);
+      dvt[dj] =
+          __builtin_amdgcn_mfma_f32_32x32x16_bf16(dot, pb, dvt[dj], 0, 0, 0);
+    }
+  }
+}
+
+template <bool MASKED, bool DROP, int D>
+DEVI void dk_tile_tr(const short* imgQ, const short* imgDO,
+                     const float* lseL, const float* dltL, int sub,
+                     int64_t q0, int64_t seq, int64_t mykv, float scale,
+                     int causal, const bf16x8 (&kfrag)[D / 16],
+                     const bf16x8 (&vfrag)[D / 16], f32x16 (&dkt)[D / 32],
+                     int lkv, int hi, const unsigned int* maskrow,
+                     int64_t mask_w, float inv_keep) {
+  // row constants as the initial accumulators: S' = Q K^T - lse/scale
+  // and dP' = dO V^T - delta.  Dropout rescales dP before the
+  // subtraction, so DROP keeps delta apart.
+  f32x16 st = load_rowconst(lseL, hi);
+  f32x16 dpt = {};
+  if (!DROP) dpt = load_rowconst(dltL, hi);
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) {
+    const int o = img_off<D>(sub + lkv, 2 * c + hi);
+    bf16x8 qf = *reinterpret_cast<const bf16x8*>(imgQ + o);
+    bf16x8 dof = *reinterpret_cast<const bf16x8*>(imgDO + o);
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfrag[c], st, 0, 0, 0);
+    dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vfrag[c], dpt, 0, 0,
+                                                  0);
+  }
+  const float c2 = scale * 1.44269504088896341f;   // P = exp2(c2 * S')
+  const RowMask rm(q0, seq, mykv, causal);
+  float ds[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float dp = dpt[r];
+    if (DROP) {
+      const int64_t qg = q0 + crow(r, hi);
+      const int64_t qgc = qg < seq ? qg : seq - 1;
+      const int64_t kvc = mykv < seq ? mykv : seq - 1;
+      const unsigned int w = maskrow[qgc * mask_w + (kvc >> 5)];
+      dp *= ((w >> (kvc & 31)) & 1u) ? inv_keep : 0.f;
+      dp += dltL[crow(r, hi)];
+    }
+    if (MASKED)
+      ds[r] = rm.masked(crow(r, hi))
+                  ? 0.f
+                  : __builtin_amdgcn_exp2f(st[r] * c2) * dp * scale;
+    else
+      ds[r] = __builtin_amdgcn_exp2f(st[r] * c2) * dp * scale;
+  }
+  bf16x8 db0 = assemble_pfrag<true>(&ds[0]);
+  bf16x8 db1 = assemble_pfrag<true>(&ds[8]);
+  const int lane = hi * 32 + lkv;
+#pragma unroll
+  for (int qc = 0; qc < 2; ++qc) {
+    bf16x8 db = qc == 0 ? db0 : db1;
+#pragma unroll
+    for (int dj = 0; dj < D / 32; ++dj) {
+      bf16x8 qt = tr_frag<D>(imgQ, sub + qc * 16, dj, lane);
+      dkt[dj] =
+          __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt, db, dkt[dj], 0, 0, 0);
+    }
+  }
+}
+
+template <bool DROP, bool DBUF, int D, bool TR>
+__global__ __launch_bounds__(256, D == 64 ? (DBUF ? 3 : 4)
+                                          : (TR && !DROP ? 3 : 2))
 void attn_bwd_dv_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ dout, const float* __restrict__ lse,
@@ -634,8 +840,13 @@ void attn_bwd_dv_kernel(
     int64_t g_sh, int64_t g_ss,
     const unsigned int* __restrict__ mask, int64_t mask_w,
     float inv_keep) {
-  __shared__ short ldsQ[DBUF ? 2 : 1][64][D + 8];
-  __shared__ short ldsDO[DBUF ? 2 : 1][64][D + 8];
+  // TR: dual-use image + the chunk's 64 -lse/scale values
+  constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
+  __shared__ __attribute__((aligned(16))) short
+      ldsQ[DBUF ? 2 : 1][64][PITCH];
+  __shared__ __attribute__((aligned(16))) short
+      ldsDO[DBUF ? 2 : 1][64][PITCH];
+  __shared__ __attribute__((aligned(16))) float ldsL[DBUF ? 2 : 1][64];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
@@ -672,7 +883,13 @@ void attn_bwd_dv_kernel(
   // global loads so they hide under this chunk's compute (the fwd v7
   // staging pattern applied to the q/dO loop).
   bf16x8 rq[2][D / 64], rdo[2][D / 64];
+  float rl = 0.f;   // TR: wave 0 carries the chunk's -lse/scale values
+  const float neg_inv_scale = -1.f / scale;
   auto prefetch = [&](int64_t q0) {
+    if (TR && wave == 0) {
+      const int64_t qr = q0 + lane;
+      rl = lsep[qr < seq ? qr : seq - 1] * neg_inv_scale;
+    }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
@@ -687,20 +904,27 @@ void attn_bwd_dv_kernel(
     }
   };
   auto commit = [&](int buf) {
+    if (TR && wave == 0) ldsL[buf][lane] = rl;
 #pragma unroll
     for (int half = 0; half < 2; ++half)
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         *reinterpret_cast<bf16x8*>(
-            &ldsQ[buf][stage_row + half * 32][stage_seg + s * 64]) =
+            img_at<TR, D>(ldsQ[buf], stage_row + half * 32,
+                          stage_seg + s * 64)) =
             rq[half][s];
         *reinterpret_cast<bf16x8*>(
-            &ldsDO[buf][stage_row + half * 32][stage_seg + s * 64]) =
+            img_at<TR, D>(ldsDO[buf], stage_row + half * 32,
+                          stage_seg + s * 64)) =
             rdo[half][s];
       }
   };
   auto stage_q64 = [&](int64_t q0) {
     __syncthreads();
+    if (TR && wave == 0) {
+      const int64_t qr = q0 + lane;
+      ldsL[0][lane] = lsep[qr < seq ? qr : seq - 1] * neg_inv_scale;
+    }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
@@ -708,11 +932,13 @@ void attn_bwd_dv_kernel(
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
-            &ldsQ[0][stage_row + half * 32][stage_seg + seg]) =
+            img_at<TR, D>(ldsQ[0], stage_row + half * 32,
+                          stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 qp + qr * in_ss + stage_seg + seg);
         *reinterpret_cast<bf16x8*>(
-            &ldsDO[0][stage_row + half * 32][stage_seg + seg]) =
+            img_at<TR, D>(ldsDO[0], stage_row + half * 32,
+                          stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 dop + qr * do_ss + stage_seg + seg);
       }
@@ -720,10 +946,26 @@ void attn_bwd_dv_kernel(
     __syncthreads();
   };
 
-  // unified 64-row chunk loop; the phase test (masked causal diagonal /
-  // branch-free bulk / masked seq tail) is block-uniform per chunk
   const unsigned int* maskrow =
       DROP ? mask + bh * seq * mask_w : (const unsigned int*)nullptr;
+  // one 32-row sub-tile from LDS buffer rb: new or legacy body
+  auto tile = [&](auto masked, int rb, int sub, int64_t q0s) {
+    constexpr bool M = decltype(masked)::value;
+    if constexpr (TR)
+      dv_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
+                             &ldsL[rb][sub], sub, q0s, seq, mykv, scale,
+                             causal, kfrag, dvt, lkv, hi, maskrow, mask_w,
+                             inv_keep);
+    else
+      dv_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, seq, mykv, scale,
+                          causal, lsep, kfrag, dvt, lkv, hi, maskrow,
+                          mask_w, inv_keep);
+  };
+  constexpr std::true_type MASKED_T{};
+  constexpr std::false_type PLAIN_T{};
+
+  // unified 64-row chunk loop; the phase test (masked causal diagonal /
+  // branch-free bulk / masked seq tail) is block-uniform per chunk
   const int64_t diag_end =
       causal ? (kv0_blk + 128 < seq ? kv0_blk + 128 : seq) : 0;
   const int64_t bulk_end = seq & ~(int64_t)63;
@@ -738,9 +980,7 @@ void attn_bwd_dv_kernel(
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t q0s = q0 + sub;
         if (q0s >= diag_end || (causal && q0s + 31 < kv0)) continue;
-        dv_tile<true, DROP, D>(ldsQ[0], ldsDO[0], sub, q0s, seq, mykv,
-                               scale, causal, lsep, kfrag, dvt, lkv, hi,
-                               maskrow, mask_w, inv_keep);
+        tile(MASKED_T, 0, sub, q0s);
       }
     }
     q0 = diag_end > q0 ? diag_end : q0;
@@ -748,9 +988,7 @@ void attn_bwd_dv_kernel(
       stage_q64(q0);
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32)
-        dv_tile<false, DROP, D>(ldsQ[0], ldsDO[0], sub, q0 + sub, seq,
-                                mykv, scale, causal, lsep, kfrag, dvt,
-                                lkv, hi, maskrow, mask_w, inv_keep);
+        tile(PLAIN_T, 0, sub, q0 + sub);
     }
     for (; q0 < seq; q0 += 64) {
       stage_q64(q0);
@@ -759,9 +997,7 @@ void attn_bwd_dv_kernel(
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t q0s = q0 + sub;
         if (q0s >= seq) break;
-        dv_tile<true, DROP, D>(ldsQ[0], ldsDO[0], sub, q0s, seq, mykv,
-                               scale, causal, lsep, kfrag, dvt, lkv, hi,
-                               maskrow, mask_w, inv_keep);
+        tile(MASKED_T, 0, sub, q0s);
       }
     }
   } else {
@@ -778,19 +1014,14 @@ void attn_bwd_dv_kernel(
       if (plain) {
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32)
-          dv_tile<false, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0 + sub,
-                                  seq, mykv, scale, causal, lsep, kfrag,
-                                  dvt, lkv, hi, maskrow, mask_w,
-                                  inv_keep);
+          tile(PLAIN_T, rb, sub, q0 + sub);
       } else if (active) {
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32) {
           const int64_t q0s = q0 + sub;
           if (q0s >= seq) break;
           if (causal && q0s + 31 < kv0) continue;
-          dv_tile<true, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, seq,
-                                 mykv, scale, causal, lsep, kfrag, dvt,
-                                 lkv, hi, maskrow, mask_w, inv_keep);
+          tile(MASKED_T, rb, sub, q0s);
         }
       }
     }
@@ -799,13 +1030,18 @@ void attn_bwd_dv_kernel(
   short* dvp = dv + (bh / heads) * g_sb + (bh % heads) * g_sh +
                mykv * g_ss;
 #pragma unroll
-  for (int dj = 0; dj < D / 32; ++dj)
+  for (int dj = 0; dj < D / 32; ++dj) {
+    if constexpr (TR) {
+      store_acc_bf16(dvp + dj * 32, dvt[dj], hi);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      dvp[dj * 32 + crow(r, hi)] = (short)f2bf(dvt[dj][r]);
+      for (int r = 0; r < 16; ++r)
+        dvp[dj * 32 + crow(r, hi)] = (short)f2bf(dvt[dj][r]);
+    }
+  }
 }
 
-template <bool DROP, bool DBUF, int D>
+template <bool DROP, bool DBUF, int D, bool TR>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -816,8 +1052,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     int64_t g_sh, int64_t g_ss,
     const unsigned int* __restrict__ mask, int64_t mask_w,
     float inv_keep) {
-  __shared__ short ldsQ[DBUF ? 2 : 1][64][D + 8];
-  __shared__ short ldsDO[DBUF ? 2 : 1][64][D + 8];
+  constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
+  __shared__ __attribute__((aligned(16))) short
+      ldsQ[DBUF ? 2 : 1][64][PITCH];
+  __shared__ __attribute__((aligned(16))) short
+      ldsDO[DBUF ? 2 : 1][64][PITCH];
+  // TR: [0] = -lse/scale, [1] = -delta of the chunk's 64 rows
+  __shared__ __attribute__((aligned(16))) float ldsL[DBUF ? 2 : 1][2][64];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
@@ -852,7 +1093,14 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 
   // staging: same DBUF pipeline as the dV kernel (see comment there)
   bf16x8 rq[2][D / 64], rdo[2][D / 64];
+  float rl = 0.f;   // TR: wave 0 carries -lse/scale, wave 1 -delta
+  const float neg_inv_scale = -1.f / scale;
   auto prefetch = [&](int64_t q0) {
+    if (TR && wave < 2) {
+      const int64_t qr = q0 + lane;
+      rl = (wave == 0 ? lsep : dltp)[qr < seq ? qr : seq - 1] *
+           (wave == 0 ? neg_inv_scale : -1.f);
+    }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
@@ -867,20 +1115,29 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     }
   };
   auto commit = [&](int buf) {
+    if (TR && wave < 2) ldsL[buf][wave][lane] = rl;
 #pragma unroll
     for (int half = 0; half < 2; ++half)
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         *reinterpret_cast<bf16x8*>(
-            &ldsQ[buf][stage_row + half * 32][stage_seg + s * 64]) =
+            img_at<TR, D>(ldsQ[buf], stage_row + half * 32,
+                          stage_seg + s * 64)) =
             rq[half][s];
         *reinterpret_cast<bf16x8*>(
-            &ldsDO[buf][stage_row + half * 32][stage_seg + s * 64]) =
+            img_at<TR, D>(ldsDO[buf], stage_row + half * 32,
+                          stage_seg + s * 64)) =
             rdo[half][s];
       }
   };
   auto stage_q64 = [&](int64_t q0) {
     __syncthreads();
+    if (TR && wave < 2) {
+      const int64_t qr = q0 + lane;
+      ldsL[0][wave][lane] =
+          (wave == 0 ? lsep : dltp)[qr < seq ? qr : seq - 1] *
+          (wave == 0 ? neg_inv_scale : -1.f);
+    }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
@@ -888,11 +1145,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
-            &ldsQ[0][stage_row + half * 32][stage_seg + seg]) =
+            img_at<TR, D>(ldsQ[0], stage_row + half * 32,
+                          stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 qp + qr * in_ss + stage_seg + seg);
         *reinterpret_cast<bf16x8*>(
-            &ldsDO[0][stage_row + half * 32][stage_seg + seg]) =
+            img_at<TR, D>(ldsDO[0], stage_row + half * 32,
+                          stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 dop + qr * do_ss + stage_seg + seg);
       }
@@ -902,6 +1161,21 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 
   const unsigned int* maskrow =
       DROP ? mask + bh * seq * mask_w : (const unsigned int*)nullptr;
+  // one 32-row sub-tile from LDS buffer rb: new or legacy body
+  auto tile = [&](auto masked, int rb, int sub, int64_t q0s) {
+    constexpr bool M = decltype(masked)::value;
+    if constexpr (TR)
+      dk_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
+                             &ldsL[rb][0][sub], &ldsL[rb][1][sub], sub,
+                             q0s, seq, mykv, scale, causal, kfrag, vfrag,
+                             dkt, lkv, hi, maskrow, mask_w, inv_keep);
+    else
+      dk_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, seq, mykv, scale,
+                          causal, lsep, dltp, kfrag, vfrag, dkt, lkv, hi,
+                          maskrow, mask_w, inv_keep);
+  };
+  constexpr std::true_type MASKED_T{};
+  constexpr std::false_type PLAIN_T{};
   const int64_t diag_end =
       causal ? (kv0_blk + 128 < seq ? kv0_blk + 128 : seq) : 0;
   const int64_t bulk_end = seq & ~(int64_t)63;
@@ -914,9 +1188,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t q0s = q0 + sub;
         if (q0s >= diag_end || (causal && q0s + 31 < kv0)) continue;
-        dk_tile<true, DROP, D>(ldsQ[0], ldsDO[0], sub, q0s, seq, mykv,
-                               scale, causal, lsep, dltp, kfrag, vfrag,
-                               dkt, lkv, hi, maskrow, mask_w, inv_keep);
+        tile(MASKED_T, 0, sub, q0s);
       }
     }
     q0 = diag_end > q0 ? diag_end : q0;
@@ -924,10 +1196,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
       stage_q64(q0);
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32)
-        dk_tile<false, DROP, D>(ldsQ[0], ldsDO[0], sub, q0 + sub, seq,
-                                mykv, scale, causal, lsep, dltp, kfrag,
-                                vfrag, dkt, lkv, hi, maskrow, mask_w,
-                                inv_keep);
+        tile(PLAIN_T, 0, sub, q0 + sub);
     }
     for (; q0 < seq; q0 += 64) {
       stage_q64(q0);
@@ -936,9 +1205,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t q0s = q0 + sub;
         if (q0s >= seq) break;
-        dk_tile<true, DROP, D>(ldsQ[0], ldsDO[0], sub, q0s, seq, mykv,
-                               scale, causal, lsep, dltp, kfrag, vfrag,
-                               dkt, lkv, hi, maskrow, mask_w, inv_keep);
+        tile(MASKED_T, 0, sub, q0s);
       }
     }
   } else {
@@ -955,20 +1222,14 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
       if (plain) {
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32)
-          dk_tile<false, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0 + sub,
-                                  seq, mykv, scale, causal, lsep, dltp,
-                                  kfrag, vfrag, dkt, lkv, hi, maskrow,
-                                  mask_w, inv_keep);
+          tile(PLAIN_T, rb, sub, q0 + sub);
       } else if (active) {
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32) {
           const int64_t q0s = q0 + sub;
           if (q0s >= seq) break;
           if (causal && q0s + 31 < kv0) continue;
-          dk_tile<true, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, seq,
-                                 mykv, scale, causal, lsep, dltp, kfrag,
-                                 vfrag, dkt, lkv, hi, maskrow, mask_w,
-                                 inv_keep);
+          tile(MASKED_T, rb, sub, q0s);
         }
       }
     }
@@ -977,10 +1238,15 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
   short* dkp = dk + (bh / heads) * g_sb + (bh % heads) * g_sh +
                mykv * g_ss;
 #pragma unroll
-  for (int dj = 0; dj < D / 32; ++dj)
+  for (int dj = 0; dj < D / 32; ++dj) {
+    if constexpr (TR) {
+      store_acc_bf16(dkp + dj * 32, dkt[dj], hi);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      dkp[dj * 32 + crow(r, hi)] = (short)f2bf(dkt[dj][r]);
+      for (int r = 0; r < 16; ++r)
+        dkp[dj * 32 + crow(r, hi)] = (short)f2bf(dkt[dj][r]);
+    }
+  }
 }
 
 // ============================================================================
@@ -1053,7 +1319,63 @@ DEVI void dq_tile(const short (&ldsK)[64][D + 8],
   }
 }
 
-template <bool DROP, bool DBUF, int D>
+// new dQ tile body (see dv_tile_tr): K/V in the dual-use image, the
+// K-transposed fragments by ds_read_b64_tr_b16, hardware bf16 convert.
+// The row constants were lane-local already.
+template <bool MASKED, bool DROP, int D>
+DEVI void dq_tile_tr(const short* imgK, const short* imgV, int sub,
+                     int64_t kv0, int64_t seq, int64_t myq, float scale,
+                     int causal, float mylse, float mydelta,
+                     const bf16x8 (&qfrag)[D / 16],
+                     const bf16x8 (&dofrag)[D / 16],
+                     f32x16 (&dqt)[D / 32], int lq, int hi,
+                     const unsigned int* maskrow, int64_t mask_w,
+                     float inv_keep) {
+  f32x16 st = {};
+  f32x16 dpt = {};
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) {
+    const int o = img_off<D>(sub + lq, 2 * c + hi);
+    bf16x8 kf = *reinterpret_cast<const bf16x8*>(imgK + o);
+    bf16x8 vf = *reinterpret_cast<const bf16x8*>(imgV + o);
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfrag[c], st, 0, 0, 0);
+    dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dofrag[c], dpt, 0, 0,
+                                                  0);
+  }
+  unsigned int mword = 0;
+  if (DROP) {
+    const int64_t qc = myq < seq ? myq : seq - 1;
+    mword = maskrow[qc * mask_w + (kv0 >> 5)];
+  }
+  float ds[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float pv = __expf(st[r] * scale - mylse);
+    if (MASKED) {
+      const int64_t kvg = kv0 + crow(r, hi);
+      if (myq >= seq || kvg >= seq || (causal && kvg > myq)) pv = 0.f;
+    }
+    float dp = dpt[r];
+    if (DROP)
+      dp *= ((mword >> crow(r, hi)) & 1u) ? inv_keep : 0.f;
+    ds[r] = pv * (dp - mydelta) * scale;
+  }
+  bf16x8 db0 = assemble_pfrag<true>(&ds[0]);
+  bf16x8 db1 = assemble_pfrag<true>(&ds[8]);
+  const int lane = hi * 32 + lq;
+#pragma unroll
+  for (int kc = 0; kc < 2; ++kc) {
+    bf16x8 db = kc == 0 ? db0 : db1;
+#pragma unroll
+    for (int dj = 0; dj < D / 32; ++dj) {
+      bf16x8 kt = tr_frag<D>(imgK, sub + kc * 16, dj, lane);
+      dqt[dj] =
+          __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt, db, dqt[dj], 0, 0, 0);
+    }
+  }
+}
+
+template <bool DROP, bool DBUF, int D, bool TR>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -1064,8 +1386,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     int64_t g_sb, int64_t g_sh, int64_t g_ss, int64_t o_sb, int64_t o_sh,
     int64_t o_ss, const unsigned int* __restrict__ mask, int64_t mask_w,
     float inv_keep, const float* __restrict__ dlse) {
-  __shared__ short ldsK[DBUF ? 2 : 1][64][D + 8];
-  __shared__ short ldsVr[DBUF ? 2 : 1][64][D + 8];
+  constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
+  __shared__ __attribute__((aligned(16))) short
+      ldsK[DBUF ? 2 : 1][64][PITCH];
+  __shared__ __attribute__((aligned(16))) short
+      ldsVr[DBUF ? 2 : 1][64][PITCH];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
@@ -1133,11 +1458,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
-            &ldsK[0][stage_row + half * 32][stage_seg + seg]) =
+            img_at<TR, D>(ldsK[0], stage_row + half * 32,
+                          stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 kp + kr * in_ss + stage_seg + seg);
         *reinterpret_cast<bf16x8*>(
-            &ldsVr[0][stage_row + half * 32][stage_seg + seg]) =
+            img_at<TR, D>(ldsVr[0], stage_row + half * 32,
+                          stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 vp + kr * in_ss + stage_seg + seg);
       }
@@ -1169,26 +1496,40 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         *reinterpret_cast<bf16x8*>(
-            &ldsK[buf][stage_row + half * 32][stage_seg + s * 64]) =
+            img_at<TR, D>(ldsK[buf], stage_row + half * 32,
+                          stage_seg + s * 64)) =
             rk[half][s];
         *reinterpret_cast<bf16x8*>(
-            &ldsVr[buf][stage_row + half * 32][stage_seg + s * 64]) =
+            img_at<TR, D>(ldsVr[buf], stage_row + half * 32,
+                          stage_seg + s * 64)) =
             rv[half][s];
       }
   };
 
   const unsigned int* maskrow =
       DROP ? mask + bh * seq * mask_w : (const unsigned int*)nullptr;
+  // one 32-key sub-tile from LDS buffer rb: new or legacy body
+  auto tile = [&](auto masked, int rb, int sub, int64_t kvs) {
+    constexpr bool M = decltype(masked)::value;
+    if constexpr (TR)
+      dq_tile_tr<M, DROP, D>(&ldsK[rb][0][0], &ldsVr[rb][0][0], sub, kvs,
+                             seq, myq, scale, causal, mylse, mydelta,
+                             qfrag, dofrag, dqt, lq, hi, maskrow, mask_w,
+                             inv_keep);
+    else
+      dq_tile<M, DROP, D>(ldsK[rb], ldsVr[rb], sub, kvs, seq, myq, scale,
+                          causal, mylse, mydelta, qfrag, dofrag, dqt, lq,
+                          hi, maskrow, mask_w, inv_keep);
+  };
+  constexpr std::true_type MASKED_T{};
+  constexpr std::false_type PLAIN_T{};
   if (!DBUF) {
     int64_t kv0 = 0;
     for (; kv0 < bulk_end; kv0 += 64) {
       stage_kv64(kv0);
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32)
-        dq_tile<false, DROP, D>(ldsK[0], ldsVr[0], sub, kv0 + sub, seq,
-                                myq, scale, causal, mylse, mydelta,
-                                qfrag, dofrag, dqt, lq, hi, maskrow,
-                                mask_w, inv_keep);
+        tile(PLAIN_T, 0, sub, kv0 + sub);
     }
     for (; kv0 < blk_kv_end; kv0 += 64) {
       stage_kv64(kv0);
@@ -1199,10 +1540,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t kvs = kv0 + sub;
         if (kvs >= wave_kv_end) break;
-        dq_tile<true, DROP, D>(ldsK[0], ldsVr[0], sub, kvs, seq, myq,
-                               scale, causal, mylse, mydelta, qfrag,
-                               dofrag, dqt, lq, hi, maskrow, mask_w,
-                               inv_keep);
+        tile(MASKED_T, 0, sub, kvs);
       }
     }
   } else {
@@ -1217,10 +1555,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
       if (kv0 < bulk_end) {
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32)
-          dq_tile<false, DROP, D>(ldsK[rb], ldsVr[rb], sub, kv0 + sub,
-                                  seq, myq, scale, causal, mylse,
-                                  mydelta, qfrag, dofrag, dqt, lq, hi,
-                                  maskrow, mask_w, inv_keep);
+          tile(PLAIN_T, rb, sub, kv0 + sub);
       } else if (active) {
         const int64_t wave_kv_end = causal
             ? (q0 + 32 < seq ? q0 + 32 : seq) : seq;
@@ -1228,10 +1563,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
         for (int sub = 0; sub < 64; sub += 32) {
           const int64_t kvs = kv0 + sub;
           if (kvs >= wave_kv_end) break;
-          dq_tile<true, DROP, D>(ldsK[rb], ldsVr[rb], sub, kvs, seq,
-                                 myq, scale, causal, mylse, mydelta,
-                                 qfrag, dofrag, dqt, lq, hi, maskrow,
-                                 mask_w, inv_keep);
+          tile(MASKED_T, rb, sub, kvs);
         }
       }
     }
@@ -1240,10 +1572,15 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
   if (!active || myq >= seq) return;
   short* dqp = dq + (bh / heads) * g_sb + (bh % heads) * g_sh + myq * g_ss;
 #pragma unroll
-  for (int dj = 0; dj < D / 32; ++dj)
+  for (int dj = 0; dj < D / 32; ++dj) {
+    if constexpr (TR) {
+      store_acc_bf16(dqp + dj * 32, dqt[dj], hi);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      dqp[dj * 32 + crow(r, hi)] = (short)f2bf(dqt[dj][r]);
+      for (int r = 0; r < 16; ++r)
+        dqp[dj * 32 + crow(r, hi)] = (short)f2bf(dqt[dj][r]);
+    }
+  }
 }
 
 }  // namespace
@@ -1350,78 +1687,59 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
     const bool dbuf = mode >= 1;
     const bool dbuf_k = mode >= 2;
     const bool dbuf_q = mode >= 3;
+    // tile bodies (EPL_ATTN_BWD_TILES): default = transposed-LDS-read
+    // tiles; "legacy" = the previous bodies, kept for a same-process
+    // A/B until a second independent run confirms the numbers
+    static const bool legacy_tiles = [] {
+      const char* e = getenv("EPL_ATTN_BWD_TILES");
+      return e != nullptr && strcmp(e, "legacy") == 0;
+    }();
+    auto launch3 = [&](auto drop_c, auto d_c, auto tr_c) {
+      constexpr bool DROP = decltype(drop_c)::value;
+      constexpr int D = decltype(d_c)::value;
+      constexpr bool TR = decltype(tr_c)::value;
+      if (D == 64 && dbuf)
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, D == 64, D, TR>), grid,
+            dim3(256), 0, stream, DV_ARGS);
+      else
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, false, D, TR>), grid,
+            dim3(256), 0, stream, DV_ARGS);
+      if (D == 64 && dbuf_q)
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(attn_bwd_dq_kernel<DROP, D == 64, D, TR>), grid,
+            dim3(256), 0, stream, DQ_ARGS);
+      else
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(attn_bwd_dq_kernel<DROP, false, D, TR>), grid,
+            dim3(256), 0, stream, DQ_ARGS);
+      if (D == 64 && dbuf_k)
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, D == 64, D, TR>), grid,
+            dim3(256), 0, stream, DK_ARGS);
+      else
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, false, D, TR>), grid,
+            dim3(256), 0, stream, DK_ARGS);
+    };
+    auto launch2 = [&](auto drop_c, auto d_c) {
+      if (legacy_tiles)
+        launch3(drop_c, d_c, std::false_type{});
+      else
+        launch3(drop_c, d_c, std::true_type{});
+    };
+    using d64 = std::integral_constant<int, 64>;
+    using d128 = std::integral_constant<int, 128>;
     if (head_dim == 128) {
-      if (drop_mask != nullptr) {
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<true, false, 128>), grid,
-            dim3(256), 0, stream, DV_ARGS);
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<true, false, 128>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<true, false, 128>), grid,
-            dim3(256), 0, stream, DK_ARGS);
-      } else {
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<false, false, 128>), grid,
-            dim3(256), 0, stream, DV_ARGS);
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<false, false, 128>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<false, false, 128>), grid,
-            dim3(256), 0, stream, DK_ARGS);
-      }
+      if (drop_mask != nullptr)
+        launch2(std::true_type{}, d128{});
+      else
+        launch2(std::false_type{}, d128{});
     } else if (drop_mask != nullptr) {
-      if (dbuf)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<true, true, 64>), grid,
-            dim3(256), 0, stream, DV_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<true, false, 64>), grid,
-            dim3(256), 0, stream, DV_ARGS);
-      if (dbuf_q)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<true, true, 64>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<true, false, 64>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-      if (dbuf_k)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<true, true, 64>), grid,
-            dim3(256), 0, stream, DK_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<true, false, 64>), grid,
-            dim3(256), 0, stream, DK_ARGS);
+      launch2(std::true_type{}, d64{});
     } else {
-      if (dbuf)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<false, true, 64>), grid,
-            dim3(256), 0, stream, DV_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<false, false, 64>), grid,
-            dim3(256), 0, stream, DV_ARGS);
-      if (dbuf_q)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<false, true, 64>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<false, false, 64>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-      if (dbuf_k)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<false, true, 64>), grid,
-            dim3(256), 0, stream, DK_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<false, false, 64>), grid,
-            dim3(256), 0, stream, DK_ARGS);
+      launch2(std::false_type{}, d64{});
     }
 #undef DV_ARGS
 #undef DQ_ARGS
@@ -1450,7 +1768,10 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
                      in_strides[2], do_strides[0], do_strides[1],
                      do_strides[2], g_strides[0], g_strides[1],
                      g_strides[2]);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_bwd_dq_kernel<false, false, 64>),
+  // the combined dK+dV kernel keeps its own body; its dQ partner runs
+  // the new tiles (a legacy A/B goes through the split path above)
+  hipLaunchKernelGGL(
+      HIP_KERNEL_NAME(attn_bwd_dq_kernel<false, false, 64, true>),
                      grid, dim3(256), 0, stream,
                      reinterpret_cast<const short*>(q),
                      reinterpret_cast<const short*>(k),

@@ -11,6 +11,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "attn_lds_image.h"
+
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
@@ -40,4 +42,43 @@ extern "C" void run_mfma_probe(const unsigned short* A,
                                hipStream_t stream) {
   hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, stream, A, B,
                      D);
+}
+
+// Transposed-LDS-read probe: one wave fills the attention backward's
+// dual-use [64][D] image with index-coded values row*256+col, then forms
+// every transposed A-operand fragment the tiles use — (sub, qc, dj) —
+// both ways: by eight 2-byte reads (the definition) and by two
+// ds_read_b64_tr_b16.  out_*[frag][lane][j], frag = (sub/32*2+qc)*(D/32)+dj.
+template <int D>
+__global__ void tr_read_probe_kernel(short* __restrict__ out_gather,
+                                     short* __restrict__ out_tr) {
+  __shared__ __attribute__((aligned(16))) short
+      img[64 * attn_img::img_pitch<D>()];
+  const int lane = threadIdx.x & 63;
+  for (int i = lane; i < 64 * D; i += 64) {
+    const int row = i / D, col = i % D;
+    img[attn_img::img_off<D>(row, col >> 3) + (col & 7)] =
+        (short)(row * 256 + col);
+  }
+  __syncthreads();
+  for (int sub = 0; sub < 64; sub += 32)
+    for (int qc = 0; qc < 2; ++qc)
+      for (int dj = 0; dj < D / 32; ++dj) {
+        const int frag = ((sub >> 5) * 2 + qc) * (D / 32) + dj;
+        const bf16x8 g =
+            attn_img::gather_frag<D>(img, sub + qc * 16, dj, lane);
+        const bf16x8 t = attn_img::tr_frag<D>(img, sub + qc * 16, dj, lane);
+        *reinterpret_cast<bf16x8*>(out_gather + (frag * 64 + lane) * 8) = g;
+        *reinterpret_cast<bf16x8*>(out_tr + (frag * 64 + lane) * 8) = t;
+      }
+}
+
+extern "C" void run_tr_read_probe(short* out_gather, short* out_tr,
+                                  int head_dim, hipStream_t stream) {
+  if (head_dim == 128)
+    hipLaunchKernelGGL(tr_read_probe_kernel<128>, dim3(1), dim3(64), 0,
+                       stream, out_gather, out_tr);
+  else
+    hipLaunchKernelGGL(tr_read_probe_kernel<64>, dim3(1), dim3(64), 0,
+                       stream, out_gather, out_tr);
 }
