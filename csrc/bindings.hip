@@ -27,6 +27,11 @@ void epl_layer_norm_bwd(void*, float*, float*, const void*, const void*,
                         const void*, const float*, const float*, float*,
                         float*, int64_t, int64_t, int64_t, bool,
                         hipStream_t);
+void epl_layer_norm_bwd_fused(void*, float*, float*, float*, const void*,
+                              const void*, const void*, const void*,
+                              const float*, const float*, float*, float*,
+                              float*, int64_t, int64_t, int64_t, bool,
+                              hipStream_t);
 void epl_bias_gelu_fwd(void*, const void*, const void*, int64_t, int64_t,
                        bool, hipStream_t);
 void epl_bias_gelu_bwd(void*, float*, const void*, const void*, const void*,
@@ -198,6 +203,65 @@ void layer_norm_bwd(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
                      gamma.data_ptr(), mean.data_ptr<float>(),
                      rstd.data_ptr<float>(), dgp, dbp, nparts, rows, cols,
                      bf16, cur_stream());
+}
+
+// layer_norm_bwd plus two optional in-kernel fusions on the bf16 fast path
+// (cols % 8 == 0, cols <= 2048):
+//   dadd       [rows, cols] bf16: dx = LNbwd(dy) + dadd, rounded once;
+//   colsum_out [cols] fp32, zero-initialised: += column sum of that dx.
+// Asking for either on another shape is an error — the caller keeps the
+// separate add / sum there.
+void layer_norm_bwd_fused(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
+                          at::Tensor dy, at::Tensor x, at::Tensor gamma,
+                          at::Tensor mean, at::Tensor rstd,
+                          c10::optional<at::Tensor> dadd,
+                          c10::optional<at::Tensor> colsum_out) {
+  const bool bf16 = is_bf16(x);
+  const int64_t cols = x.size(-1);
+  const int64_t rows = x.numel() / cols;
+  TORCH_CHECK(!bf16 || cols % 8 == 0, "bf16 LayerNorm needs cols % 8 == 0");
+  TORCH_CHECK((size_t)cols * 2 * sizeof(float) <= 128 * 1024,
+              "LayerNorm backward supports cols <= 16384");
+  check(dgamma, at::kFloat, "dgamma");
+  check(dbeta, at::kFloat, "dbeta");
+  TORCH_CHECK(dx.numel() == x.numel() && dy.numel() == x.numel());
+  TORCH_CHECK(dgamma.numel() == cols && dbeta.numel() == cols);
+  const bool fast = bf16 && cols % 8 == 0 && cols <= 2048;
+  const bool fused = dadd.has_value() || colsum_out.has_value();
+  TORCH_CHECK(fast || !fused,
+              "layer_norm_bwd_fused: dadd/colsum_out need the bf16 fast "
+              "path (cols % 8 == 0, cols <= 2048)");
+  const void* dadd_p = nullptr;
+  float* cs_out = nullptr;
+  if (dadd.has_value()) {
+    check(*dadd, x.scalar_type(), "dadd");
+    TORCH_CHECK(dadd->numel() == x.numel(), "dadd shape mismatch");
+    dadd_p = dadd->data_ptr();
+  }
+  if (colsum_out.has_value()) {
+    check(*colsum_out, at::kFloat, "colsum_out");
+    TORCH_CHECK(colsum_out->numel() == cols, "colsum_out shape mismatch");
+    cs_out = colsum_out->data_ptr<float>();
+  }
+  float* dgp = nullptr;
+  float* dbp = nullptr;
+  float* csp = nullptr;
+  at::Tensor ws;
+  int64_t nparts = 0;
+  if (fast) {
+    const int64_t wave_rows = (rows + 3) / 4;
+    nparts = (wave_rows < 1024 ? wave_rows : 1024) * 4;
+    ws = at::empty({cs_out ? 3 : 2, nparts, cols}, dgamma.options());
+    dgp = ws.data_ptr<float>();
+    dbp = dgp + nparts * cols;
+    if (cs_out) csp = dbp + nparts * cols;
+  }
+  epl_layer_norm_bwd_fused(dx.data_ptr(), dgamma.data_ptr<float>(),
+                           dbeta.data_ptr<float>(), cs_out, dy.data_ptr(),
+                           x.data_ptr(), gamma.data_ptr(), dadd_p,
+                           mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                           dgp, dbp, csp, nparts, rows, cols, bf16,
+                           cur_stream());
 }
 
 void bias_gelu_fwd(at::Tensor out, at::Tensor x, at::Tensor bias) {
@@ -491,6 +555,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lamb_phase2", &lamb_phase2);
   m.def("layer_norm_fwd", &layer_norm_fwd);
   m.def("layer_norm_bwd", &layer_norm_bwd);
+  m.def("layer_norm_bwd_fused", &layer_norm_bwd_fused, py::arg("dx"),
+        py::arg("dgamma"), py::arg("dbeta"), py::arg("dy"), py::arg("x"),
+        py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
+        py::arg("dadd") = py::none(), py::arg("colsum_out") = py::none());
   m.def("bias_gelu_fwd", &bias_gelu_fwd);
   m.def("bias_gelu_bwd", &bias_gelu_bwd);
   m.def("ce_rowstats", &ce_rowstats);

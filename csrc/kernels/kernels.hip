@@ -371,21 +371,64 @@ __global__ void layer_norm_fwd_kernel(
 
 // bf16 fast backward: ONE ROW PER WAVE — no barriers at all.  Each wave
 // reduces its row with shuffles, keeps the row image in registers between
-// the reduction and the dx pass (HBM read-once/write-once), accumulates
-// dgamma/dbeta in registers across its rows and flushes once with
-// atomics.  CHUNKS = ceil(cols/8/64); fast path cols <= 1024 (CHUNKS<=2).
-template <int CHUNKS, bool CACHE>
-__global__ __launch_bounds__(256, 2) void layer_norm_bwd_bf16_kernel(
+// the reduction and the dx pass (HBM read-once/write-once; CHUNKS=4
+// re-reads the row from L2 instead), accumulates dgamma/dbeta in
+// registers across its rows and writes them once as one partial row per
+// wave — no atomics here; ln_bwd_partial_reduce_kernel sums the partial
+// rows.  CHUNKS = ceil(cols/8/64), cols <= 2048.
+//   DADD   : dx += dadd (bf16 [rows, cols]) in fp32 before the single
+//            bf16 rounding — the gradient arriving through the summed
+//            stream of a fused-residual LN.
+//   COLSUM : a third accumulator, the column sum of the fp32 value that
+//            is rounded into dx (DADD included), written to cs_part —
+//            the bias gradient of the Linear that produced x.
+// With both flags off the instruction stream is the two-plane kernel's.
+// The waves-per-SIMD bound pins each CHUNKS to the occupancy its plain
+// form reaches (5 / 3 / 3); to fit the extra plane under it the fused
+// forms stop holding gamma as fp32 registers where those are short:
+// CHUNKS=1 keeps it packed bf16 (4 VGPRs, unpacked at each use), CHUNKS=4
+// stages it once per block in LDS (4 KB).
+template <int CHUNKS, bool CACHE, bool DADD, bool COLSUM>
+__global__ __launch_bounds__(256, CHUNKS == 1 ? 5 : 3) void
+layer_norm_bwd_bf16_kernel(
     void* __restrict__ dx, float* __restrict__ dg_part,
-    float* __restrict__ db_part, const void* __restrict__ dy,
-    const void* __restrict__ x, const void* __restrict__ gamma,
+    float* __restrict__ db_part, float* __restrict__ cs_part,
+    const void* __restrict__ dy, const void* __restrict__ x,
+    const void* __restrict__ gamma, const void* __restrict__ dadd,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
     int64_t rows, int64_t cols) {
   using T = unsigned short;
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;               // wave in block (0..3)
   const int wpb = blockDim.x >> 6;                // waves per block
-  float8 gw[CHUNKS], acc_dg[CHUNKS], acc_db[CHUNKS];
+  constexpr bool FUSED = DADD || COLSUM;
+  constexpr bool G_LDS = FUSED && CHUNKS == 4;    // gamma from LDS
+  constexpr bool G_PK = FUSED && CHUNKS == 1;     // gamma packed in VGPRs
+  constexpr bool G_F32 = !G_LDS && !G_PK;
+  __shared__ __attribute__((aligned(16))) T g_lds[G_LDS ? CHUNKS * 512 : 8];
+  float8 gw[G_F32 ? CHUNKS : 1], acc_dg[CHUNKS], acc_db[CHUNKS];
+  uint4 gpk[G_PK ? CHUNKS : 1];
+  float8 acc_cs[COLSUM ? CHUNKS : 1];
+  if (G_LDS) {
+    for (int64_t c = (int64_t)threadIdx.x * 8; c < cols;
+         c += (int64_t)blockDim.x * 8)
+      *reinterpret_cast<uint4*>(g_lds + c) =
+          *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(gamma) +
+                                          c);
+    __syncthreads();
+  }
+  // gamma of chunk k (columns c .. c+7) as fp32
+  auto gamma_at = [&](int k, int64_t c) -> float8 {
+    if (G_LDS) return load_bf16x8(g_lds + c);
+    if (G_PK) {
+      // opaque to the optimizer, or it hoists the unpack out of the row
+      // loop and the eight fp32 registers are back
+      asm volatile("" : "+v"(gpk[k].x), "+v"(gpk[k].y), "+v"(gpk[k].z),
+                   "+v"(gpk[k].w));
+      return load_bf16x8(reinterpret_cast<const T*>(&gpk[k]));
+    }
+    return gw[k];
+  };
 #pragma unroll
   for (int k = 0; k < CHUNKS; ++k) {
     const int64_t c = ((int64_t)lane + k * 64) * 8;
@@ -393,9 +436,15 @@ __global__ __launch_bounds__(256, 2) void layer_norm_bwd_bf16_kernel(
     for (int j = 0; j < 8; ++j) {
       acc_dg[k].v[j] = 0.f;
       acc_db[k].v[j] = 0.f;
+      if (COLSUM) acc_cs[k].v[j] = 0.f;
     }
-    if (c < cols)
-      gw[k] = load_bf16x8(reinterpret_cast<const T*>(gamma) + c);
+    if (c < cols) {
+      if (G_F32)
+        gw[k] = load_bf16x8(reinterpret_cast<const T*>(gamma) + c);
+      if (G_PK)
+        gpk[k] = *reinterpret_cast<const uint4*>(
+            reinterpret_cast<const T*>(gamma) + c);
+    }
   }
   for (int64_t row = (int64_t)blockIdx.x * wpb + wid; row < rows;
        row += (int64_t)gridDim.x * wpb) {
@@ -410,10 +459,11 @@ __global__ __launch_bounds__(256, 2) void layer_norm_bwd_bf16_kernel(
       if (c >= cols) continue;
       float8 d = load_bf16x8(reinterpret_cast<const T*>(dy) + base + c);
       float8 f = load_bf16x8(reinterpret_cast<const T*>(x) + base + c);
+      const float8 g = gamma_at(k, c);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xhat = (f.v[j] - mean) * rstd;
-        const float dyg = d.v[j] * gw[k].v[j];
+        const float dyg = d.v[j] * g.v[j];
         if (CACHE) {
           c_xhat[k].v[j] = xhat;
           c_dy[k].v[j] = d.v[j];
@@ -448,13 +498,24 @@ __global__ __launch_bounds__(256, 2) void layer_norm_bwd_bf16_kernel(
           xh.v[j] = (f.v[j] - mean) * rstd;
         }
       }
+      const float8 g = gamma_at(k, c);
       float8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float dyg = dv.v[j] * gw[k].v[j];
+        const float dyg = dv.v[j] * g.v[j];
         o.v[j] = (dyg - (sum_dyg + xh.v[j] * sum_dygx) * inv_cols) * rstd;
         acc_dg[k].v[j] += dv.v[j] * xh.v[j];
         acc_db[k].v[j] += dv.v[j];
+      }
+      if (DADD) {
+        const float8 a =
+            load_bf16x8(reinterpret_cast<const T*>(dadd) + base + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o.v[j] += a.v[j];
+      }
+      if (COLSUM) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc_cs[k].v[j] += o.v[j];
       }
       store_bf16x8(reinterpret_cast<T*>(dx) + base + c, o);
     }
@@ -467,26 +528,32 @@ __global__ __launch_bounds__(256, 2) void layer_norm_bwd_bf16_kernel(
     if (c >= cols) continue;
     store_f32x8(dg_part + prow + c, acc_dg[k]);
     store_f32x8(db_part + prow + c, acc_db[k]);
+    if (COLSUM) store_f32x8(cs_part + prow + c, acc_cs[k]);
   }
 }
 
-// reduce the [nparts, cols] partial buffers into dgamma/dbeta.
+// reduce the [nparts, cols] partial buffers into dgamma/dbeta (and, with
+// COLSUM, the third plane into colsum).
 // grid = (col_chunks, PSPLIT): each block sums a strided slice of the
 // partial rows for its 256-column range (coalesced row-major reads) and
 // contributes one atomicAdd per column (PSPLIT per column total).
+template <bool COLSUM>
 __global__ void ln_bwd_partial_reduce_kernel(
     float* __restrict__ dgamma, float* __restrict__ dbeta,
-    const float* __restrict__ dg_part, const float* __restrict__ db_part,
+    float* __restrict__ colsum, const float* __restrict__ dg_part,
+    const float* __restrict__ db_part, const float* __restrict__ cs_part,
     int64_t nparts, int64_t cols) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
-  float sg = 0.f, sb = 0.f;
+  float sg = 0.f, sb = 0.f, sc = 0.f;
   for (int64_t p = blockIdx.y; p < nparts; p += gridDim.y) {
     sg += dg_part[p * cols + c];
     sb += db_part[p * cols + c];
+    if (COLSUM) sc += cs_part[p * cols + c];
   }
   atomicAdd(&dgamma[c], sg);
   atomicAdd(&dbeta[c], sb);
+  if (COLSUM) atomicAdd(&colsum[c], sc);
 }
 
 // generic (fp32 / large-cols) backward: LDS partials + global re-read
@@ -577,6 +644,48 @@ DEV float gelu_grad_f(float x) {
   return 0.5f * (1.f + t) + 0.5f * x * dt;
 }
 
+// ---- bf16 paths: lean arithmetic -------------------------------------------
+// With u = k0 (x + k1 x^3):  0.5 (1 + tanh u) = 1 / (1 + e^{-2u}) =: s, so
+//   gelu(x)  = x s
+//   gelu'(x) = s + x s (1 - s) (2 k0 + 6 k0 k1 x^2)
+// e^{-2u} is ONE v_exp_f32 (exp2 with -2 k0 log2(e) folded into the cubic)
+// and s ONE v_rcp_f32 — no IEEE division, no tanh.  Both are ~1 ulp fp32,
+// far inside the bf16 rounding of the result.  x -> -inf side: e = +inf,
+// s = 0; x -> +inf side: e = 0, s = 1.
+DEV float gelu_sigmoid(float x) {
+  constexpr float c0 = (float)(-2.0 * 0.7978845608028654 *
+                               1.4426950408889634);  // -2 sqrt(2/pi) log2(e)
+  constexpr float c1 = (float)(-2.0 * 0.7978845608028654 *
+                               1.4426950408889634 * 0.044715);
+  const float e = __builtin_amdgcn_exp2f(x * (c0 + c1 * x * x));
+  return __builtin_amdgcn_rcpf(1.f + e);
+}
+
+DEV float gelu_lean(float x) { return x * gelu_sigmoid(x); }
+
+DEV float gelu_grad_lean(float x) {
+  constexpr float d0 = (float)(2.0 * 0.7978845608028654);  // 2 sqrt(2/pi)
+  constexpr float d1 = (float)(6.0 * 0.7978845608028654 * 0.044715);
+  const float s = gelu_sigmoid(x);
+  return s + x * s * (1.f - s) * (d0 + d1 * x * x);
+}
+
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16v2 = __attribute__((ext_vector_type(2))) __bf16;
+
+// two floats -> packed bf16 pair in one v_cvt_pk_bf16_f32 (the same
+// round-to-nearest-even as f2bf for finite values)
+DEV unsigned int cvt_pk_bf16(float a, float b) {
+  f32x2 f = {a, b};
+  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f, bf16v2));
+}
+
+DEV void store_bf16x8_pk(unsigned short* p, const float8& f) {
+  *reinterpret_cast<uint4*>(p) =
+      make_uint4(cvt_pk_bf16(f.v[0], f.v[1]), cvt_pk_bf16(f.v[2], f.v[3]),
+                 cvt_pk_bf16(f.v[4], f.v[5]), cvt_pk_bf16(f.v[6], f.v[7]));
+}
+
 template <bool BF16>
 __global__ void bias_gelu_fwd_kernel(void* __restrict__ out,
                                      const void* __restrict__ x,
@@ -585,17 +694,24 @@ __global__ void bias_gelu_fwd_kernel(void* __restrict__ out,
   using T = unsigned short;
   const int64_t n = rows * cols;
   if (BF16) {
-    const int64_t nvec = n / 8;
-    for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
-         i += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t base = i * 8;
+    // Each thread owns ONE 8-column vector and strides by whole rows, so
+    // its bias stays in registers and the loop has no modulo: the first
+    // rpp * vpr threads tile rpp consecutive rows (flat, coalesced), the
+    // few left over idle.  The launcher guarantees rpp >= 1.
+    const unsigned vpr = (unsigned)(cols / 8);            // vectors per row
+    const unsigned g = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned rpp = (gridDim.x * blockDim.x) / vpr;  // rows per pass
+    const unsigned r0 = g / vpr;
+    if (r0 >= rpp) return;
+    const int64_t c = (int64_t)(g - r0 * vpr) * 8;
+    const float8 b = load_bf16x8(reinterpret_cast<const T*>(bias) + c);
+    for (int64_t row = r0; row < rows; row += rpp) {
+      const int64_t base = row * cols + c;
       float8 f = load_bf16x8(reinterpret_cast<const T*>(x) + base);
-      float8 b = load_bf16x8(reinterpret_cast<const T*>(bias) +
-                             (base % cols));
       float8 o;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) o.v[k] = gelu_f(f.v[k] + b.v[k]);
-      store_bf16x8(reinterpret_cast<T*>(out) + base, o);
+      for (int k = 0; k < 8; ++k) o.v[k] = gelu_lean(f.v[k] + b.v[k]);
+      store_bf16x8_pk(reinterpret_cast<T*>(out) + base, o);
     }
   } else {
     for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -638,11 +754,11 @@ __global__ void bias_gelu_bwd_bf16_kernel(
     float8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float g = d.v[j] * gelu_grad_f(f.v[j] + bw.v[j]);
+      const float g = d.v[j] * gelu_grad_lean(f.v[j] + bw.v[j]);
       o.v[j] = g;
       acc.v[j] += g;
     }
-    store_bf16x8(reinterpret_cast<T*>(dx) + base, o);
+    store_bf16x8_pk(reinterpret_cast<T*>(dx) + base, o);
   }
   store_f32x8(db_part + wave_id * 512 + (int64_t)lane * 8, acc);
 }
@@ -966,6 +1082,38 @@ __global__ void colsum_reduce_kernel(void* __restrict__ db,
     reinterpret_cast<float*>(db)[c] = s;
 }
 
+// LN fast backward + partial reduce for one (DADD, COLSUM) combination
+template <bool DADD, bool COLSUM>
+static void ln_bwd_fast_launch(void* dx, float* dgamma, float* dbeta,
+                               float* colsum, const void* dy, const void* x,
+                               const void* gamma, const void* dadd,
+                               const float* mean, const float* rstd,
+                               float* dg_part, float* db_part,
+                               float* cs_part, int64_t rows, int64_t cols,
+                               hipStream_t stream) {
+  const int64_t wave_rows = (rows + 3) / 4;
+  const int grid = (int)(wave_rows < 1024 ? wave_rows : 1024);
+  if (cols <= 512)
+    hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<1, true, DADD, COLSUM>),
+                       dim3(grid), dim3(256), 0, stream, dx, dg_part,
+                       db_part, cs_part, dy, x, gamma, dadd, mean, rstd,
+                       rows, cols);
+  else if (cols <= 1024)
+    hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<2, true, DADD, COLSUM>),
+                       dim3(grid), dim3(256), 0, stream, dx, dg_part,
+                       db_part, cs_part, dy, x, gamma, dadd, mean, rstd,
+                       rows, cols);
+  else
+    hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<4, false, DADD, COLSUM>),
+                       dim3(grid), dim3(256), 0, stream, dx, dg_part,
+                       db_part, cs_part, dy, x, gamma, dadd, mean, rstd,
+                       rows, cols);
+  hipLaunchKernelGGL(ln_bwd_partial_reduce_kernel<COLSUM>,
+                     dim3((unsigned)((cols + 255) / 256), 64), dim3(256), 0,
+                     stream, dgamma, dbeta, colsum, dg_part, db_part,
+                     cs_part, (int64_t)grid * 4, cols);
+}
+
 // extern "C" launchers (raw pointers + stream; bound to torch in bindings.hip)
 // ============================================================================
 extern "C" {
@@ -1087,30 +1235,37 @@ void epl_layer_norm_fwd(void* out, const void* x, const void* res,
   }
 }
 
-void epl_layer_norm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy,
-                        const void* x, const void* gamma, const float* mean,
-                        const float* rstd, float* dg_part, float* db_part,
-                        int64_t nparts, int64_t rows, int64_t cols,
-                        bool bf16, hipStream_t stream) {
+// dadd / colsum (with its cs_part plane) are optional and only valid on
+// the bf16 fast path (cols % 8 == 0, cols <= 2048); the caller checks.
+void epl_layer_norm_bwd_fused(void* dx, float* dgamma, float* dbeta,
+                              float* colsum, const void* dy, const void* x,
+                              const void* gamma, const void* dadd,
+                              const float* mean, const float* rstd,
+                              float* dg_part, float* db_part,
+                              float* cs_part, int64_t nparts, int64_t rows,
+                              int64_t cols, bool bf16, hipStream_t stream) {
   if (bf16 && cols % 8 == 0 && cols <= 2048 && dg_part != nullptr) {
-    const int64_t wave_rows = (rows + 3) / 4;
-    const int grid = (int)(wave_rows < 1024 ? wave_rows : 1024);
-    if (cols <= 512)
-      hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<1, true>), dim3(grid),
-                         dim3(256), 0, stream, dx, dg_part, db_part, dy, x,
-                         gamma, mean, rstd, rows, cols);
-    else if (cols <= 1024)
-      hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<2, true>), dim3(grid),
-                         dim3(256), 0, stream, dx, dg_part, db_part, dy, x,
-                         gamma, mean, rstd, rows, cols);
-    else
-      hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<4, false>),
-                         dim3(grid), dim3(256), 0, stream, dx, dg_part,
-                         db_part, dy, x, gamma, mean, rstd, rows, cols);
-    hipLaunchKernelGGL(ln_bwd_partial_reduce_kernel,
-                       dim3((unsigned)((cols + 255) / 256), 64), dim3(256),
-                       0, stream, dgamma, dbeta, dg_part, db_part,
-                       (int64_t)grid * 4, cols);
+    const bool has_cs = colsum != nullptr && cs_part != nullptr;
+    if (dadd != nullptr) {
+      if (has_cs)
+        ln_bwd_fast_launch<true, true>(dx, dgamma, dbeta, colsum, dy, x,
+                                       gamma, dadd, mean, rstd, dg_part,
+                                       db_part, cs_part, rows, cols, stream);
+      else
+        ln_bwd_fast_launch<true, false>(dx, dgamma, dbeta, colsum, dy, x,
+                                        gamma, dadd, mean, rstd, dg_part,
+                                        db_part, cs_part, rows, cols, stream);
+    } else {
+      if (has_cs)
+        ln_bwd_fast_launch<false, true>(dx, dgamma, dbeta, colsum, dy, x,
+                                        gamma, dadd, mean, rstd, dg_part,
+                                        db_part, cs_part, rows, cols, stream);
+      else
+        ln_bwd_fast_launch<false, false>(dx, dgamma, dbeta, colsum, dy, x,
+                                         gamma, dadd, mean, rstd, dg_part,
+                                         db_part, cs_part, rows, cols,
+                                         stream);
+    }
     return;
   }
   int grid = (int)(rows < 1024 ? rows : 1024);
@@ -1125,14 +1280,27 @@ void epl_layer_norm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy,
                        dy, x, gamma, mean, rstd, rows, cols);
 }
 
+void epl_layer_norm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy,
+                        const void* x, const void* gamma, const float* mean,
+                        const float* rstd, float* dg_part, float* db_part,
+                        int64_t nparts, int64_t rows, int64_t cols,
+                        bool bf16, hipStream_t stream) {
+  epl_layer_norm_bwd_fused(dx, dgamma, dbeta, nullptr, dy, x, gamma, nullptr,
+                           mean, rstd, dg_part, db_part, nullptr, nparts,
+                           rows, cols, bf16, stream);
+}
+
 void epl_bias_gelu_fwd(void* out, const void* x, const void* bias,
                        int64_t rows, int64_t cols, bool bf16,
                        hipStream_t stream) {
-  const int grid = grid_for((rows * cols + 7) / 8);
-  if (bf16)
+  int grid = grid_for((rows * cols + 7) / 8);
+  if (bf16) {
+    // the kernel tiles whole rows: it needs at least one row of threads
+    const int min_grid = (int)((cols / 8 + kBlock - 1) / kBlock);
+    if (grid < min_grid) grid = min_grid;
     hipLaunchKernelGGL(bias_gelu_fwd_kernel<true>, dim3(grid), dim3(kBlock), 0,
                        stream, out, x, bias, rows, cols);
-  else
+  } else
     hipLaunchKernelGGL(bias_gelu_fwd_kernel<false>, dim3(grid), dim3(kBlock),
                        0, stream, out, x, bias, rows, cols);
 }

@@ -25,7 +25,8 @@ _NATIVE_ATTN = os.environ.get("EPL_NATIVE_ATTENTION", "auto")
 
 from easyparallellibrary_amd.ops.bias_gelu import FusedBiasGelu
 from easyparallellibrary_amd.ops.bias_linear import FusedBiasLinear
-from easyparallellibrary_amd.ops.layer_norm import FusedLayerNorm
+from easyparallellibrary_amd.ops.layer_norm import (FusedLayerNorm,
+                                                    linear_for_ln)
 
 # Linear bias grads via the fused colsum kernel.  The kernel wins per-op
 # (vs torch's ~2.2 TB/s reduce) but the path loses end-to-end: r1 592 vs
@@ -79,7 +80,15 @@ class SelfAttention(nn.Module):
         self.proj = _Linear(hidden, hidden)
         self.dropout = dropout
 
-    def forward(self, x):
+    def forward(self, x, bias_grad_to_ln=False):
+        """bias_grad_to_ln: the caller feeds the result straight into a
+        FusedLayerNorm and takes (out, lin_bias) — see linear_for_ln."""
+        o = self._attend(x)
+        if bias_grad_to_ln:
+            return linear_for_ln(self.proj, o)
+        return self.proj(o)
+
+    def _attend(self, x):
         from easyparallellibrary_amd.ops.attention import (
             flash_attention, qkv_flash_attention, qkv_native_ok)
         b, s, h = x.shape
@@ -91,8 +100,7 @@ class SelfAttention(nn.Module):
             # slices directly — no unbind/stack copies at all; dropout
             # runs in-kernel (philox keep-mask, p quantized to 1/256)
             o = qkv_flash_attention(qkv, causal=self.causal, dropout_p=p)
-            o = o.transpose(1, 2).reshape(b, s, h)
-            return self.proj(o)
+            return o.transpose(1, 2).reshape(b, s, h)
         if _QKV_SPLIT:
             q, k, v = _QKVSplit.apply(qkv)
         else:
@@ -102,8 +110,7 @@ class SelfAttention(nn.Module):
             v = v.transpose(1, 2)
         o = flash_attention(q, k, v, causal=self.causal,
                             allow_native=native_here, dropout_p=p)
-        o = o.transpose(1, 2).reshape(b, s, h)
-        return self.proj(o)
+        return o.transpose(1, 2).reshape(b, s, h)
 
 
 class MLP(nn.Module):
@@ -115,8 +122,11 @@ class MLP(nn.Module):
         self.act = FusedBiasGelu(ffn_hidden)
         self.fc2 = _Linear(ffn_hidden, hidden)
 
-    def forward(self, x):
-        return self.fc2(self.act(self.fc1(x)))
+    def forward(self, x, bias_grad_to_ln=False):
+        h = self.act(self.fc1(x))
+        if bias_grad_to_ln:
+            return linear_for_ln(self.fc2, h)
+        return self.fc2(h)
 
 
 class Block(nn.Module):
@@ -132,16 +142,27 @@ class Block(nn.Module):
         self.ln2 = FusedLayerNorm(hidden)
         self.mlp = MLP(hidden, ffn_hidden)
 
+    @staticmethod
+    def _into_ln(mod, cls, x):
+        """mod(x) for a FusedLayerNorm consumer -> (out, lin_bias); a
+        wrapped or replaced submodule runs as the plain call it expects."""
+        if type(mod) is cls:
+            return mod(x, bias_grad_to_ln=True)
+        return mod(x), None
+
     def forward(self, x):
         if self.pre_ln:
             # residual add fused into ln2; the summed stream s is the
             # residual carried forward
-            a = self.attn(self.ln1(x))
-            y, s = self.ln2.forward_with_sum(a, x)
+            a, pb = self._into_ln(self.attn, SelfAttention, self.ln1(x))
+            y, s = self.ln2.forward_with_sum(a, x, lin_bias=pb)
             return s + self.mlp(y)
-        # post-LN: both residual adds fuse into the LN kernels
-        x = self.ln1(self.attn(x), residual=x)
-        x = self.ln2(self.mlp(x), residual=x)
+        # post-LN: both residual adds fuse into the LN kernels, and the
+        # LN backward returns the bias gradient of the Linear before it
+        a, pb = self._into_ln(self.attn, SelfAttention, x)
+        x = self.ln1(a, residual=x, lin_bias=pb)
+        m, fb = self._into_ln(self.mlp, MLP, x)
+        x = self.ln2(m, residual=x, lin_bias=fb)
         return x
 
 

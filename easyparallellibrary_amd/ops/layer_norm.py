@@ -8,15 +8,28 @@ the fp32 row image in LDS between the statistics and normalize passes
 (no HBM re-read), and — with a residual input — folds the residual add
 into the same pass, eliminating the separate elementwise-add kernel
 entirely (post-LN BERT: x = LN(x + sublayer(x))).  The backward caches
-xhat / dy*gamma in LDS and flushes dgamma/dbeta once per block.
+xhat / dy in registers, writes dgamma/dbeta as per-wave partial rows
+that a small kernel reduces, and can fold two neighbours in: the
+gradient arriving through the summed stream (dx += ds) and the bias
+gradient of the Linear that produced x (column sum of dx).
 CPU fallback = identical math in torch (numerics tests compare against a
 plain fp32 torch reference).
 """
 
+import os
+
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from easyparallellibrary_amd.ops.dispatch import native_ext, use_native
+
+
+# EPL_LN_BWD_FUSE: "1" (default) = blocks hand the bias gradient of the
+# Linear feeding a LayerNorm to the LN backward kernel (its column sum of
+# dx) instead of a separate reduction; "0" = every Linear reduces its own
+# bias gradient.  Read once; the A/B and the tests flip it.
+_LN_BWD_FUSE = os.environ.get("EPL_LN_BWD_FUSE", "1") == "1"
 
 
 def _native_ok(x):
@@ -24,12 +37,50 @@ def _native_ok(x):
             and x.shape[-1] % 8 == 0)
 
 
+def _bwd_fast_ok(x):
+    """Shapes the one-row-per-wave backward kernel takes — the only ones
+    with the in-kernel dadd / colsum."""
+    return (_native_ok(x) and x.dtype == torch.bfloat16
+            and x.shape[-1] <= 2048)
+
+
+def layer_norm_bwd_fused(dy, x, gamma, mean, rstd, dadd=None,
+                         want_colsum=False):
+    """Native LN backward of ``dy`` at the saved (x, mean, rstd), plus
+    ``dadd`` added into dx and, if asked, colsum = dx.sum(rows) in fp32.
+    Fast-path shapes do both inside the kernel; the others keep the
+    separate add and sum.  Returns (dx, dgamma, dbeta, colsum | None)."""
+    cols = x.shape[-1]
+    dx = torch.empty_like(x)
+    dgamma = torch.zeros(cols, dtype=torch.float32, device=x.device)
+    dbeta = torch.zeros(cols, dtype=torch.float32, device=x.device)
+    if _bwd_fast_ok(x):
+        colsum = (torch.zeros(cols, dtype=torch.float32, device=x.device)
+                  if want_colsum else None)
+        if dadd is not None:
+            dadd = dadd.contiguous().to(x.dtype)
+        native_ext().layer_norm_bwd_fused(dx, dgamma, dbeta, dy, x, gamma,
+                                          mean, rstd, dadd, colsum)
+        return dx, dgamma, dbeta, colsum
+    native_ext().layer_norm_bwd(dx, dgamma, dbeta, dy, x, gamma, mean, rstd)
+    if dadd is not None:
+        dx = dx + dadd
+    colsum = (dx.reshape(-1, cols).sum(dim=0, dtype=torch.float32)
+              if want_colsum else None)
+    return dx, dgamma, dbeta, colsum
+
+
 class _FusedLayerNorm(torch.autograd.Function):
     """y = LN(x (+ residual)).  When residual is given, also returns the
-    sum s = x + residual (the pre-LN residual stream)."""
+    sum s = x + residual (the pre-LN residual stream).
+
+    ``lin_bias`` (optional) is the bias parameter of the Linear that
+    produced x, whose forward ran with that bias detached.  It does not
+    enter the forward math; its gradient is the column sum of dx, which
+    the backward kernel accumulates next to dgamma/dbeta."""
 
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps):
+    def forward(ctx, x, residual, gamma, beta, eps, lin_bias=None):
         x = x.contiguous()
         cols = x.shape[-1]
         rows = x.numel() // cols
@@ -62,6 +113,12 @@ class _FusedLayerNorm(torch.autograd.Function):
             s = norm_in if has_res else None
         ctx.save_for_backward(norm_in, gamma, mean, rstd)
         ctx.has_res = has_res
+        ctx.bias_dtype = lin_bias.dtype if lin_bias is not None else None
+        ctx.fuse = _LN_BWD_FUSE
+        if ctx.fuse:
+            # an unused output (post-LN drops s) must not cost a zero
+            # fill and an add of zeros in backward
+            ctx.set_materialize_grads(False)
         if has_res:
             return out, s
         return out
@@ -71,17 +128,24 @@ class _FusedLayerNorm(torch.autograd.Function):
         norm_in, gamma, mean, rstd = ctx.saved_tensors
         # with residual, grad also flows through the returned sum s
         ds = rest[0] if (ctx.has_res and rest) else None
-        dy = dy.contiguous()
+        # switch off: the summed stream's gradient is added separately
+        ds_late = None
+        if not ctx.fuse:
+            ds, ds_late = None, ds
+        want_db = ctx.bias_dtype is not None and ctx.needs_input_grad[5]
         cols = norm_in.shape[-1]
         rows = norm_in.numel() // cols
-        if _native_ok(norm_in):
-            dx = torch.empty_like(norm_in)
-            dgamma = torch.zeros(cols, dtype=torch.float32,
-                                 device=norm_in.device)
-            dbeta = torch.zeros(cols, dtype=torch.float32,
-                                device=norm_in.device)
-            native_ext().layer_norm_bwd(dx, dgamma, dbeta, dy, norm_in,
-                                        gamma.contiguous(), mean, rstd)
+        dgamma = dbeta = colsum = None
+        if dy is None:
+            # only the summed stream was used: LN contributes nothing
+            dx = ds
+            if dx is not None and want_db:
+                colsum = dx.reshape(rows, cols).sum(dim=0,
+                                                    dtype=torch.float32)
+        elif _native_ok(norm_in):
+            dx, dgamma, dbeta, colsum = layer_norm_bwd_fused(
+                dy.contiguous(), norm_in, gamma.contiguous(), mean, rstd,
+                dadd=ds, want_colsum=want_db)
         else:
             xf = norm_in.float().reshape(rows, cols)
             dyf = dy.float().reshape(rows, cols)
@@ -89,18 +153,23 @@ class _FusedLayerNorm(torch.autograd.Function):
             dyg = dyf * gamma.float()
             c1 = dyg.mean(dim=1, keepdim=True)
             c2 = (dyg * xhat).mean(dim=1, keepdim=True)
-            dx = ((dyg - c1 - xhat * c2) * rstd[:, None]).to(norm_in.dtype)
-            dx = dx.reshape(norm_in.shape)
+            dxf = (dyg - c1 - xhat * c2) * rstd[:, None]
+            if ds is not None:
+                # one rounding, as the kernel's in-register add
+                dxf = dxf + ds.float().reshape(rows, cols)
+            if want_db:
+                colsum = dxf.sum(dim=0)
+            dx = dxf.to(norm_in.dtype).reshape(norm_in.shape)
             dgamma = (dyf * xhat).sum(dim=0)
             dbeta = dyf.sum(dim=0)
-        if ds is not None:
-            dx = dx + ds
-        if ctx.has_res:
-            # d(x) == d(residual) — the add distributes the gradient
-            return (dx, dx, dgamma.to(ctx.param_dtype),
-                    dbeta.to(ctx.param_dtype), None)
-        return (dx, None, dgamma.to(ctx.param_dtype),
-                dbeta.to(ctx.param_dtype), None)
+        if dgamma is not None:
+            dgamma = dgamma.to(ctx.param_dtype)
+            dbeta = dbeta.to(ctx.param_dtype)
+        if ds_late is not None:
+            dx = dx + ds_late
+        dbias = colsum.to(ctx.bias_dtype) if colsum is not None else None
+        # d(x) == d(residual) — the add distributes the gradient
+        return (dx, dx if ctx.has_res else None, dgamma, dbeta, None, dbias)
 
 
 class FusedLayerNorm(nn.Module):
@@ -110,19 +179,38 @@ class FusedLayerNorm(nn.Module):
         self.bias = nn.Parameter(torch.zeros(hidden))
         self.eps = eps
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, lin_bias=None):
         """ln(x) — or, with residual, ln(x + residual) (fused).  The
         fused form returns only the normalized output; use
-        forward_with_sum when the summed stream is needed (pre-LN)."""
+        forward_with_sum when the summed stream is needed (pre-LN).
+
+        lin_bias: bias parameter of the Linear that produced x, when
+        that Linear ran with the bias detached (see linear_for_ln): its
+        gradient then comes out of this LN's backward."""
         if residual is None:
             return _FusedLayerNorm.apply(x, None, self.weight, self.bias,
-                                         self.eps)
+                                         self.eps, lin_bias)
         out, _ = _FusedLayerNorm.apply(x, residual, self.weight, self.bias,
-                                       self.eps)
+                                       self.eps, lin_bias)
         return out
 
-    def forward_with_sum(self, x, residual):
+    def forward_with_sum(self, x, residual, lin_bias=None):
         """(ln(x+residual), x+residual) — pre-LN blocks keep the sum as
         the residual stream."""
         return _FusedLayerNorm.apply(x, residual, self.weight, self.bias,
-                                     self.eps)
+                                     self.eps, lin_bias)
+
+
+def linear_for_ln(lin, x):
+    """Run ``lin`` on x for a consumer that is a FusedLayerNorm.
+
+    Returns (y, lin_bias).  When the LN backward can deliver the bias
+    gradient (plain nn.Linear whose bias requires grad, switch on),
+    the forward runs with the bias detached — same GEMM, same bias
+    epilogue, same result — so autograd skips the Linear's own bias
+    reduction, and lin_bias is the parameter to hand to the LN.
+    Otherwise (y, None): the Linear runs as the module it is."""
+    if (_LN_BWD_FUSE and type(lin) is nn.Linear and lin.bias is not None
+            and lin.bias.requires_grad and torch.is_grad_enabled()):
+        return F.linear(x, lin.weight, lin.bias.detach()), lin.bias
+    return lin(x), None
