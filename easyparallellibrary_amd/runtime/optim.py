@@ -177,11 +177,17 @@ class FusedLAMB:
             g.state["exp_avg_sq"] = torch.zeros_like(g.master_arena)
             g.state["lamb_update"] = torch.zeros_like(g.master_arena)
             nchunks = len(g.ordered)
-            # per-8-element chunk index map (kernel indexes chunk_of[i>>3])
-            cmap = torch.empty((g.total + 7) // 8, dtype=torch.int32)
-            for ci, (p, off) in enumerate(zip(g.ordered, g.offsets)):
-                end = off + p.numel()
-                cmap[off // 8:(end + 7) // 8] = ci
+            # per-8-element chunk index map (kernel indexes chunk_of[i>>3]
+            # for EVERY arena element and adds into the norm buffers at
+            # that index, so the alignment padding after a parameter must
+            # carry a valid chunk id too: it belongs to the parameter in
+            # front of it, whose norms its zeros do not change)
+            assert g.total % 8 == 0 and all(o % 8 == 0 for o in g.offsets), \
+                "LAMB chunk map needs 8-element aligned arena offsets"
+            cmap = torch.zeros(g.total // 8, dtype=torch.int32)
+            ends = list(g.offsets[1:]) + [g.total]
+            for ci, (off, end) in enumerate(zip(g.offsets, ends)):
+                cmap[off // 8:end // 8] = ci
             g.state["lamb_chunk_of"] = cmap.to(g.master_arena.device)
             g.state["lamb_nchunks"] = nchunks
 

@@ -171,11 +171,8 @@ def test_ring_module_native_gpu():
     assert torch.isfinite(x.grad.float()).all()
 
 
-def test_moe_native_dispatch_matches_torch_path():
-    """The fused dispatch/combine kernels (csrc/kernels/moe.hip) must
-    match the torch index path exactly-ish: same output, same x / gate
-    / expert-weight grads (fp32-accumulated combine vs bf16 index_add
-    gives small rounding differences)."""
+def _moe_native_vs_torch(hidden, ffn, top_k, capacity_factor,
+                         expect_over_capacity):
     import os
     import easyparallellibrary_amd as epl
     from easyparallellibrary_amd.ops import moe as moe_mod
@@ -186,11 +183,22 @@ def test_moe_native_dispatch_matches_torch_path():
     def run(native):
         os.environ["EPL_MOE_NATIVE_DISPATCH"] = "1" if native else "0"
         torch.manual_seed(10)
-        m = ExpertParallelMLP(512, 2048, 8).to("cuda", torch.bfloat16)
-        x = torch.randn(4, 256, 512, device="cuda", dtype=torch.bfloat16,
+        m = ExpertParallelMLP(hidden, ffn, 8, top_k=top_k,
+                              capacity_factor=capacity_factor).to(
+                                  "cuda", torch.bfloat16)
+        x = torch.randn(4, 256, hidden, device="cuda", dtype=torch.bfloat16,
                         requires_grad=True)
         y = m(x)
         y.float().pow(2).mean().backward()
+        if expect_over_capacity:
+            # from the gate's own output: some expert was chosen more
+            # often than it has slots, so the in-kernel skip ran
+            with torch.no_grad():
+                probs = m.gate(x.reshape(-1, hidden)).float().softmax(-1)
+                topi = probs.topk(top_k, dim=-1).indices.reshape(-1)
+            counts = torch.bincount(topi, minlength=8)
+            cap = max(1, int(capacity_factor * 1024 * top_k / 8))
+            assert int(counts.max()) > cap, (counts.tolist(), cap)
         return (y.detach().float(), x.grad.float().clone(),
                 m.gate.weight.grad.float().clone(),
                 m.w1.grad.float().clone())
@@ -206,6 +214,21 @@ def test_moe_native_dispatch_matches_torch_path():
     assert torch.allclose(ggn, ggt, atol=3e-2,
                           rtol=3e-2), (ggn - ggt).abs().max()
     assert torch.allclose(gw1n, gw1t, atol=3e-2), (gw1n - gw1t).abs().max()
+
+
+def test_moe_native_dispatch_matches_torch_path():
+    """The fused dispatch/combine kernels (csrc/kernels/moe.hip) must
+    match the torch index path exactly-ish: same output, same x / gate
+    / expert-weight grads (fp32-accumulated combine vs bf16 index_add
+    gives small rounding differences)."""
+    _moe_native_vs_torch(512, 2048, 2, 1.25, expect_over_capacity=False)
+
+
+def test_moe_native_dispatch_matches_torch_path_over_capacity():
+    """Same comparison, same tolerances, at hidden 520 (the column loop's
+    second pass runs with one active lane), top-1 gating and capacity
+    factor 0.25: three quarters of the assignments are over capacity."""
+    _moe_native_vs_torch(520, 1040, 1, 0.25, expect_over_capacity=True)
 
 
 def test_gpt2_tiny_convergence_200_steps():

@@ -1,0 +1,247 @@
+"""The fp64 references and input builders of kernel_refs.py, validated
+without a GPU: each reference against an independent torch formulation,
+and each builder against the properties the GPU tests rely on."""
+
+import pytest
+import torch
+
+from tests import kernel_refs as kr
+
+F64 = torch.float64
+
+
+# ---- LAMB -----------------------------------------------------------------
+def _cpu_lamb_group(dtype=torch.float32):
+    from easyparallellibrary_amd.parallel.dp import FlatParamGroup
+    from easyparallellibrary_amd.runtime.optim import FusedLAMB
+    params = kr.lamb_params(dtype=dtype)
+    g = FlatParamGroup(params, torch.device("cpu"))
+    return g, FusedLAMB
+
+
+@pytest.mark.parametrize("wd", [0.01, 0.0])
+@pytest.mark.parametrize("grad_scale", [1.0, 1024.0])
+def test_lamb_ref_matches_step_torch(wd, grad_scale):
+    g, FusedLAMB = _cpu_lamb_group()
+    opt = FusedLAMB([g], lr=1e-2, weight_decay=wd)
+    ext = kr.lamb_extents(g)
+    mag = kr.lamb_elem_magnitude(g)
+    kr.lamb_fill(g, seed=10, scale_weights=True, grad_mul=0.0)
+    master = g.master_arena.to(F64).clone()
+    m = torch.zeros_like(master)
+    v = torch.zeros_like(master)
+    for step in (1, 2, 3):
+        kr.lamb_fill(g, seed=10 + step, grad_mul=grad_scale,
+                     zero_grad_chunk=1 if step == 1 else None)
+        r = kr.lamb_ref(master, g.grad_arena.to(F64), m, v, ext, opt.lr,
+                        opt.beta1, opt.beta2, opt.eps, wd, step,
+                        1.0 / grad_scale)
+        opt.step(grad_scale=grad_scale)
+        # the zero parameter has ||w|| = 0 at step 1; at wd = 0 the
+        # zero-gradient parameter has ||u|| = 0: both take ratio 1
+        if step == 1:
+            zc = [c for c, (o, n) in enumerate(ext)
+                  if not master[o:o + n].any()]
+            assert len(zc) == 1 and r["wsq"][zc[0]] == 0
+            assert r["ratio"][zc[0]] == 1.0
+            if wd == 0.0:
+                assert r["usq"][1] == 0 and r["ratio"][1] == 1.0
+                assert torch.equal(r["master"][ext[1][0]:sum(ext[1])],
+                                   master[ext[1][0]:sum(ext[1])])
+        tol = 1e-6 * mag + 1e-5 * r["master"].abs()
+        assert ((g.master_arena.to(F64) - r["master"]).abs() <= tol).all()
+        assert ((g.state["exp_avg"].to(F64) - r["m"]).abs()
+                <= 1e-6 * mag + 1e-5 * r["m"].abs()).all()
+        assert ((g.state["exp_avg_sq"].to(F64) - r["v"]).abs()
+                <= 1e-6 * mag + 1e-5 * r["v"]).all()
+        master, m, v = r["master"], r["m"], r["v"]
+
+
+def test_lamb_ref_known_values():
+    """One element, hand-computed: step 1 gives mhat = g, vhat = g^2."""
+    master = torch.tensor([2.0, -1.0], dtype=F64)
+    grad = torch.tensor([3.0, 0.5], dtype=F64) * 8
+    z = torch.zeros(2, dtype=F64)
+    r = kr.lamb_ref(master, grad, z, z, [(0, 1), (1, 1)], 0.1, 0.9, 0.999,
+                    0.0, 0.5, 1, 1 / 8)
+    u = torch.tensor([1.0 + 0.5 * 2.0, 1.0 - 0.5], dtype=F64)
+    assert torch.allclose(r["update"], u, rtol=1e-12)
+    assert torch.allclose(r["ratio"], torch.tensor([1.0, 2.0], dtype=F64),
+                          rtol=1e-12)
+    assert torch.allclose(r["master"], master - 0.1 * r["ratio"] * u,
+                          rtol=1e-12)
+
+
+def test_lamb_chunk_map_covers_padding():
+    """chunk_of is read for padding elements as well and indexes the norm
+    buffers: no entry may be left unset."""
+    g, FusedLAMB = _cpu_lamb_group(torch.bfloat16)
+    FusedLAMB([g])
+    kr.check_chunk_map(g)
+    # the arena the GPU tests use: padded extents, 128-aligned
+    assert [e for _, e in kr.lamb_padded_extents(g)] == \
+        [4096, 384, 128, 2176, 256, 128]
+    assert g.master_arena is not g.param_arena
+
+
+# ---- cross-entropy --------------------------------------------------------
+CE_CASES = [(5, [8]), (5, [7]), (37, [2048, 2056, 1001]), (1, [264, 264]),
+            (4097, [264, 256])]
+
+
+@pytest.mark.parametrize("ignore_index", [-100, 0])
+def test_ce_ref_matches_torch(ignore_index):
+    logits, targets, dloss, _ = kr.ce_case(37, [40, 48, 9], F64,
+                                           ignore_index)
+    loss, dlogits = kr.ce_ref(logits, targets, ignore_index, dloss, 0.5)
+    lr = logits.clone().requires_grad_(True)
+    want = torch.nn.functional.cross_entropy(
+        lr, targets, ignore_index=ignore_index, reduction="none")
+    want.backward(dloss.to(F64) * 0.5)
+    assert torch.allclose(loss, want, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(dlogits, lr.grad, rtol=1e-12, atol=1e-14)
+    ign = targets == ignore_index
+    assert ign.any() and (loss[ign] == 0).all()
+    assert (dlogits[ign] == 0).all()
+
+
+def test_ce_shard_stats_merge_to_full_loss():
+    widths = [40, 48, 9]
+    logits, targets, _, _ = kr.ce_case(37, widths, F64)
+    loss, _ = kr.ce_ref(logits, targets, -100)
+    stats, b = [], 0
+    for w in widths:
+        stats.append(kr.ce_shard_stats_ref(logits[:, b:b + w], targets, b,
+                                           -100))
+        b += w
+    gmax = torch.stack([s[0] for s in stats]).max(dim=0).values
+    gsum = sum(s[1] * torch.exp(s[0] - gmax) for s in stats)
+    tl = sum(s[2] for s in stats)
+    merged = torch.where(targets != -100, gsum.log() + gmax - tl,
+                         torch.zeros_like(gmax))
+    assert torch.allclose(merged, loss, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("rows,widths", CE_CASES)
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_ce_case_properties(rows, widths, dtype):
+    ignore_index = 0 if rows == 37 else -100
+    logits, targets, dloss, special = kr.ce_case(rows, widths, dtype,
+                                                 ignore_index)
+    vocab = sum(widths)
+    assert logits.shape == (rows, vocab) and logits.dtype == dtype
+    live = targets != ignore_index
+    assert int(targets[live].min()) >= 0 and int(targets[live].max()) < vocab
+    assert (targets[6::7] == ignore_index).all()
+    req = kr.ce_required_targets(widths)
+    n_live = sum(1 for r in range(rows) if r % 7 != 6)
+    for t in req[:n_live]:
+        assert (targets == t).any(), t
+    if rows >= 7:
+        # both sides of every shard edge, the last column, class 0
+        assert len(req) == 2 * len(widths) and len(req) <= n_live
+    lf = logits.to(F64)
+    plain = torch.ones(rows, dtype=torch.bool)
+    for r in special.values():
+        plain[r] = False
+    assert lf[plain].abs().max() <= 8
+    if "hot" in special:
+        assert lf[special["hot"]].min() >= 96
+    if "equal" in special:
+        assert (lf[special["equal"]] == lf[special["equal"]][0]).all()
+    for name, gap in (("gap60", 60), ("gap120", 120)):
+        if name in special:
+            r = special[name]
+            others = lf[r, widths[0]:].max()
+            # bf16 rounds the peak by up to 2**-8 relative
+            assert lf[r, kr.CE_PEAK_COL] - others >= gap - 0.5
+            assert targets[r] != kr.CE_PEAK_COL
+    if len(widths) > 1 and rows > kr.CE_GAP120:
+        assert set(special) == {"hot", "gap60", "equal", "gap120"}
+        # the far shards' rescaled sum is 0 in fp32 for the wide gap
+        assert torch.exp(torch.tensor(-119.5, dtype=torch.float32)) \
+            * vocab == 0
+    assert dloss.dtype == torch.float32
+    assert dloss.unique().numel() > rows // 2      # non-uniform
+
+
+# ---- MoE ------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(kr.MOE_PATTERNS))
+def test_moe_pattern_properties(name):
+    pattern, k, cap = kr.MOE_PATTERNS[name]
+    fe, pos, ft, inv, fw = kr.moe_assignment(96, k, 4, cap, pattern)
+    kr.moe_check_claims(name, fe, pos, ft, inv, k, 4, cap, 96)
+    assert fw.dtype == torch.float32 and fw.unique().numel() == fw.numel()
+    assert fw.min() > 0.1 and fw.max() < 0.9
+
+
+@pytest.mark.parametrize("pattern,k,cap", [("uneven1", 1, 20000),
+                                           ("skew", 2, 40000)])
+def test_moe_grid_stride_lists(pattern, k, cap):
+    n = 70000
+    fe, pos, ft, inv, fw = kr.moe_assignment(n, k, 4, cap, pattern)
+    kr.moe_check_lists(fe, pos, ft, inv, k, 4, n)
+    props = kr.moe_properties(fe, pos, ft, k, 4, cap, n)
+    assert n > 65536 and props["dropped"] > 0
+    assert fw.unique().numel() > n // 2   # fp32 spacing merges a few
+
+
+@pytest.mark.parametrize("top_k,cf", [(2, 1.25), (2, 0.5), (1, 0.25)])
+def test_moe_refs_match_module_torch_path(top_k, cf):
+    """dispatch ref -> expert FFN -> combine ref equals ExpertParallelMLP's
+    torch index path (what EPL_MOE_NATIVE_DISPATCH=0 computes), fp64."""
+    import easyparallellibrary_amd as epl
+    from easyparallellibrary_amd.ops.moe import ExpertParallelMLP
+    epl.init()
+    torch.manual_seed(0)
+    hidden, ffn, E, n = 16, 24, 4, 40
+    mod = ExpertParallelMLP(hidden, ffn, E, top_k=top_k,
+                            capacity_factor=cf).double()
+    x = torch.randn(n, hidden, dtype=F64)
+    with torch.no_grad():
+        want = mod(x)
+        probs = mod.gate(x).float().softmax(dim=-1)
+        topv, topi = probs.topk(top_k, dim=-1)
+        topv = topv / topv.sum(dim=-1, keepdim=True)
+        cap = max(1, int(cf * n * top_k / E))
+        fe, pos, ft, inv, order = kr.moe_assignment_from_topi(topi, E)
+        kr.moe_check_lists(fe, pos, ft, inv, top_k, E, n)
+        fw = topv.reshape(-1)[order]
+        if cf < 1:
+            assert (pos >= cap).any()
+        disp, written = kr.moe_dispatch_fwd_ref(x, fe, pos, ft, E, cap)
+        assert (disp[~written] == 0).all()
+        h = torch.stack([
+            torch.nn.functional.gelu(disp[e] @ mod.w1[e]) @ mod.w2[e]
+            for e in range(E)])
+        out, _ = kr.moe_combine_fwd_ref(h, fw, fe, pos, ft, n, cap)
+    assert torch.allclose(out, want, rtol=1e-10, atol=1e-12)
+
+
+def test_moe_backward_refs_are_the_adjoints():
+    """<dispatch(x), g> = <x, dispatch_bwd(g)>, and combine_bwd is the
+    gradient of <combine(h, fw), dout> by autograd."""
+    n, k, E, cap, hidden = 96, 2, 4, 10, 8
+    fe, pos, ft, inv, fw = kr.moe_assignment(n, k, E, cap, "skew")
+    gen = torch.Generator().manual_seed(1)
+    x = torch.randn(n, hidden, generator=gen, dtype=F64)
+    g = torch.randn(E, cap, hidden, generator=gen, dtype=F64)
+    disp, _ = kr.moe_dispatch_fwd_ref(x, fe, pos, ft, E, cap)
+    dx = kr.moe_dispatch_bwd_ref(g, fe, pos, ft, n, cap)
+    assert torch.allclose((disp * g).sum(), (x * dx).sum(), rtol=1e-12)
+
+    h = torch.randn(E, cap, hidden, generator=gen,
+                    dtype=F64).requires_grad_(True)
+    fwd = fw.to(F64).requires_grad_(True)
+    dout = torch.randn(n, hidden, generator=gen, dtype=F64)
+    keep = pos < cap
+    out = torch.zeros(n, hidden, dtype=F64).index_add(
+        0, ft[keep], h[fe[keep], pos[keep]] * fwd[keep][:, None])
+    ref_out, _ = kr.moe_combine_fwd_ref(h.detach(), fw, fe, pos, ft, n, cap)
+    assert torch.allclose(out.detach(), ref_out, rtol=1e-12)
+    out.backward(dout)
+    dh, dfw, _ = kr.moe_combine_bwd_ref(dout, h.detach(), fw, fe, pos, ft,
+                                        E, cap)
+    assert torch.allclose(dh, h.grad, rtol=1e-12, atol=1e-14)
+    assert torch.allclose(dfw, fwd.grad, rtol=1e-12, atol=1e-14)
+    assert (dfw[~keep] == 0).all()

@@ -44,6 +44,72 @@ def test_fused_adamw_matches_torch():
     assert torch.allclose(pbf.float(), ref_p, atol=1e-2, rtol=1e-2)
 
 
+def _adamw_ref64(master, grad, m, v, lr, b1, b2, eps, wd, step, inv_scale):
+    """fp64 AdamW step, FusedAdamW._step_torch's definition."""
+    g = grad * inv_scale
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    mh = m / (1 - b1 ** step)
+    vh = v / (1 - b2 ** step)
+    master = master - lr * (mh / (vh.sqrt() + eps) + wd * master)
+    return master, m, v
+
+
+def _adamw_case(n, grad_dtype, with_bf16, lo=0, hi=None):
+    """Three steps of _C.fused_adamw on [lo:hi) of n-element arenas with
+    the AMP unscale (gradients pre-multiplied by 1024, inv_scale 1/1024)
+    against fp64 at test_fused_adamw_matches_torch's tolerances."""
+    hi = n if hi is None else hi
+    f64 = torch.float64
+    gen = torch.Generator().manual_seed(7)
+    master = torch.randn(n, generator=gen).to(dev())
+    grad = (torch.randn(n, generator=gen) * 1024).to(grad_dtype).to(dev())
+    m = torch.zeros(n, device=dev())
+    v = torch.zeros(n, device=dev())
+    pbf = master.to(torch.bfloat16) if with_bf16 else None
+    before = [t.clone() for t in (master, m, v)] + \
+        ([pbf.clone()] if with_bf16 else [])
+    rp, rm, rv = (t[lo:hi].cpu().to(f64) for t in (master, m, v))
+    g64 = grad[lo:hi].cpu().to(f64)
+    lr, b1, b2, eps, wd = 1e-3, 0.9, 0.999, 1e-8, 0.01
+    for step in (1, 2, 3):
+        _C.fused_adamw(master[lo:hi], pbf[lo:hi] if with_bf16 else None,
+                       grad[lo:hi], m[lo:hi], v[lo:hi], lr, b1, b2, eps, wd,
+                       step, 1.0 / 1024)
+        rp, rm, rv = _adamw_ref64(rp, g64, rm, rv, lr, b1, b2, eps, wd,
+                                  step, 1.0 / 1024)
+    torch.cuda.synchronize()
+    for got, want in ((master, rp), (m, rm), (v, rv)):
+        assert torch.allclose(got[lo:hi].cpu().to(f64), want, atol=1e-6,
+                              rtol=1e-5)
+    after = [master, m, v] + ([pbf] if with_bf16 else [])
+    if with_bf16:
+        assert torch.equal(pbf[lo:hi], master[lo:hi].to(torch.bfloat16))
+        assert torch.allclose(pbf[lo:hi].cpu().to(f64), rp, atol=1e-2,
+                              rtol=1e-2)
+    for a, b in zip(after, before):
+        assert torch.equal(a[:lo], b[:lo]) and torch.equal(a[hi:], b[hi:])
+        assert not torch.equal(a[lo:hi], b[lo:hi])
+
+
+# 12345: vector body + scalar tail; 8 * 256 * 4096 + 13: one vector past a
+# full pass of the capped grid, plus a scalar tail
+@pytest.mark.parametrize("n", [12345, 8 * 256 * 4096 + 13])
+@pytest.mark.parametrize("grad_dtype,with_bf16", [
+    (torch.float32, True), (torch.bfloat16, False), (torch.float32, False)])
+def test_fused_adamw_variants(grad_dtype, with_bf16, n):
+    _adamw_case(n, grad_dtype, with_bf16)
+
+
+@pytest.mark.parametrize("grad_dtype,with_bf16", [
+    (torch.bfloat16, True), (torch.float32, True), (torch.bfloat16, False),
+    (torch.float32, False)])
+def test_fused_adamw_slice(grad_dtype, with_bf16):
+    """As FusedAdamW.step / eager_apply issue it: the kernel runs on a
+    128-aligned slice of every arena and leaves the rest bit-identical."""
+    _adamw_case(1024, grad_dtype, with_bf16, lo=128, hi=640)
+
+
 @pytest.mark.parametrize("dtype,cols,rows", [
     (torch.bfloat16, 1024, 512), (torch.float32, 1024, 512),
     (torch.bfloat16, 512, 512), (torch.bfloat16, 1600, 512),
@@ -165,6 +231,36 @@ def test_scale_and_casts():
     _C.sqnorm(src, out)
     torch.cuda.synchronize()
     assert torch.allclose(out, (src * src).sum().reshape(1), rtol=1e-4)
+
+
+def test_scale_bf16_exact():
+    """n = 1001: 125 vectors and a one-element tail."""
+    torch.manual_seed(4)
+    x = torch.randn(1001, device=dev()).to(torch.bfloat16)
+    want = (x.float() * 0.5).to(torch.bfloat16)
+    _C.scale_(x, 0.5)
+    torch.cuda.synchronize()
+    assert torch.equal(x, want)
+    y = (torch.randn(1001, device=dev()) * 3).to(torch.bfloat16)
+    want = (y.float() * 0.3).to(torch.bfloat16)   # a rounding scale
+    _C.scale_(y, 0.3)
+    torch.cuda.synchronize()
+    assert torch.equal(y, want)
+
+
+@pytest.mark.parametrize("dtype,n", [
+    (torch.bfloat16, 777), (torch.bfloat16, 1024 * 256 + 77),
+    (torch.float32, 1024 * 256 + 77)])
+def test_sqnorm_dtypes_and_grid_stride(dtype, n):
+    """bf16 input, and more elements than the 1024-block grid covers in
+    one pass, against the fp64 sum."""
+    torch.manual_seed(4)
+    src = torch.randn(n, device=dev()).to(dtype)
+    out = torch.zeros(1, device=dev())
+    _C.sqnorm(src, out)
+    torch.cuda.synchronize()
+    want = (src.double() ** 2).sum().reshape(1)
+    assert torch.allclose(out.double(), want, rtol=1e-4, atol=0)
 
 
 def test_rccl_single_rank_comm():
