@@ -358,6 +358,19 @@ static void attn_strides(const at::Tensor& t, int64_t* out3,
   out3[2] = t.stride(2);
 }
 
+// The attention kernels put one of (batch*heads, 128-row blocks) on
+// gridDim.y, which holds at most 65535 blocks: non-causal launches carry
+// batch*heads there, causal ones the row blocks (the combined dK+dV kernel
+// is non-causal only).  A launch past the limit fails without a trace and
+// leaves the outputs unwritten, so refuse it here.
+static void attn_check_grid(int64_t bh, int64_t seq, bool causal) {
+  const int64_t nqb = (seq + 127) / 128;
+  TORCH_CHECK(nqb <= 65535, "attention: seq ", seq, " needs ", nqb,
+              " 128-row blocks, more than the 65535 a launch can hold");
+  TORCH_CHECK(causal || bh <= 65535, "attention: non-causal batch*heads ",
+              bh, " exceeds the 65535 blocks of gridDim.y");
+}
+
 // drop_mask: optional int32 [bh*seq*ceil(seq/32)] keep-bit tensor the
 // kernel fills when dropout is on (drop_thresh in (0,256); the actual
 // drop probability is drop_thresh/256).
@@ -380,6 +393,7 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
   const int64_t seq = q.size(2);
   const int64_t head_dim = q.size(3);
   const int64_t bh = q.size(0) * heads;
+  attn_check_grid(bh, seq, causal);
   unsigned int* mptr = nullptr;
   int64_t mask_w = (seq + 31) / 32;
   if (drop_mask.has_value()) {
@@ -416,6 +430,7 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
   const int64_t heads = q.size(1);
   const int64_t seq = q.size(2);
   const int64_t bh = q.size(0) * heads;
+  attn_check_grid(bh, seq, causal);
   check(delta_ws, at::kFloat, "delta_ws");
   const unsigned int* mptr = nullptr;
   int64_t mask_w = (seq + 31) / 32;

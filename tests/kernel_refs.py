@@ -1,5 +1,6 @@
 """Plain fp64 references and deterministic input builders for the HIP
-kernel tests (LAMB phases, sharded cross-entropy, MoE dispatch/combine).
+kernel tests (LAMB phases, sharded cross-entropy, MoE dispatch/combine,
+flash attention with its derived per-element rounding bounds).
 
 Everything here runs on the CPU in float64 and is validated without a GPU
 by test_kernel_refs_cpu.py; the GPU tests compare the kernels against it.
@@ -399,3 +400,343 @@ def moe_combine_bwd_ref(dout, h, fw, fe, pos, ft, num_experts, cap):
     dfw[keep] = (d * hk).sum(dim=1)
     mag[keep] = (d * hk).abs().sum(dim=1)
     return dh, dfw, mag
+
+
+# ---------------------------------------------------------------------------
+# Flash attention
+# ---------------------------------------------------------------------------
+ATTN_B, ATTN_H = 2, 3      # b != h, so bh / heads vs bh % heads shows
+U_BF16 = 2.0 ** -8          # bf16 unit roundoff used by attn_bounds
+ATTN_SENTINEL16 = 0x7FA5    # a bf16 NaN: a stray read poisons the result
+ATTN_SENTINEL32 = 0x7FA55AA5  # an fp32 NaN
+ATTN_FAMILIES = ("randn", "peaked", "shifted")
+ATTN_LAYOUTS = ("plain", "qkv", "padded")
+ATTN_PEAK_KEYS = (0, 31, 32, 63, 64, 127, 128)
+# the GPU matrix (test_attention_fp64_gpu.py); test_kernel_refs_cpu.py
+# proves the bounds on the same cases
+ATTN_DIMS = (64, 128)
+ATTN_SEQS = (1, 31, 32, 33, 64, 65, 72, 127, 128, 129, 200, 257)
+ATTN_CROSSED_SEQS = (72, 200)     # every layout
+ATTN_DROP_SEQS = (33, 72, 200, 257)
+ATTN_DROP_FAMILY = {1: "randn", 128: "peaked", 255: "shifted"}
+ATTN_DLSE_SEQS = (72, 200)
+ATTN_COMBINED_SEQS = (33, 64, 72, 200, 257)
+ATTN_ENV_SEQS = (72, 200, 257)
+ATTN_OUTPUTS = ("out", "lse", "delta", "dq", "dk", "dv")
+# allowed err / E: the derived bound is proven at 1 x E for the rounding
+# model on the CPU; the kernels get twice that on the bf16 outputs
+ATTN_FACTOR = dict(out=2.0, lse=1.0, delta=1.0, dq=2.0, dk=2.0, dv=2.0)
+
+
+def attn_env_cases(dbuf):
+    """(d, seq, causal, thresh, family) run by the child process of one
+    EPL_ATTN_BWD_DBUF setting: d128 always stages directly, so it runs in
+    the dbuf-0 children only; the families rotate"""
+    dims = ATTN_DIMS if dbuf == 0 else (64,)
+    cases = [(d, seq, causal, thresh)
+             for d in dims for seq in ATTN_ENV_SEQS
+             for causal in (False, True) for thresh in (0, 128)]
+    return [c + (ATTN_FAMILIES[i % len(ATTN_FAMILIES)],)
+            for i, c in enumerate(cases)]
+
+
+def attn_inv_keep(thresh):
+    return 256.0 / (256 - thresh)
+
+
+def attn_ratio(err, bound):
+    """worst err / bound over the elements; 0 / 0 counts as 0 and a
+    non-zero error at a zero bound as inf"""
+    r = torch.where(err == 0, torch.zeros_like(err), err / bound)
+    return float(r.max()) if bool(torch.isfinite(err).all()) else \
+        float("inf")
+
+
+def bf16_round(x):
+    """fp64 -> nearest bf16 (ties to even) -> fp64"""
+    return x.to(torch.float32).to(torch.bfloat16).to(F64)
+
+
+def attn_valid(sq, sk, causal):
+    valid = torch.ones(sq, sk, dtype=torch.bool)
+    return torch.tril(valid) if causal else valid
+
+
+def attn_ref(q, k, v, dout, causal, scale, keep=None, inv_keep=1.0,
+             dlse=None, valid=None):
+    """Softmax attention forward and backward by explicit fp64 formulas
+    (no autograd).  q, dout: [B,H,Sq,D]; k, v: [B,H,Sk,D]; keep: [B,H,Sq,Sk]
+    0/1 dropout keep bits or None; dlse: [B,H,Sq] cotangent of lse or None;
+    valid: [Sq,Sk] bool key mask overriding ``causal`` (used by the mutation
+    tests).  delta follows the dQ kernel: rowsum(dout o out) - dlse."""
+    assert q.dtype == F64 and k.dtype == F64 and v.dtype == F64
+    if valid is None:
+        valid = attn_valid(q.shape[-2], k.shape[-2], causal)
+    s = torch.matmul(q, k.transpose(-1, -2)) * scale
+    sm = s.masked_fill(~valid, float("-inf"))
+    mx = sm.max(dim=-1, keepdim=True).values
+    e = torch.exp(sm - mx)
+    l = e.sum(dim=-1, keepdim=True)
+    lse = (mx + l.log()).squeeze(-1)
+    p = e / l
+    pd = p if keep is None else p * keep * inv_keep
+    out = torch.matmul(pd, v)
+    dl = torch.zeros_like(lse) if dlse is None else dlse
+    delta = (dout * out).sum(dim=-1) - dl
+    dp = torch.matmul(dout, v.transpose(-1, -2))
+    if keep is not None:
+        dp = dp * keep * inv_keep
+    ds = p * (dp - delta.unsqueeze(-1)) * scale
+    return dict(s=s, lse=lse, P=p, Pd=pd, out=out, delta=delta, dP=dp,
+                dS=ds, dq=torch.matmul(ds, k),
+                dk=torch.matmul(ds.transpose(-1, -2), q),
+                dv=torch.matmul(pd.transpose(-1, -2), dout),
+                dlse=dl, valid=valid)
+
+
+def attn_delta_ref(dout, out_used, dlse=None):
+    """delta = rowsum(dout o out_used) - dlse in fp64 and its bound: the
+    kernel sums the d products of the bf16 ``out_used`` it reads in fp32."""
+    prod = dout * out_used
+    dl = torch.zeros(prod.shape[:-1], dtype=F64) if dlse is None else dlse
+    return (prod.sum(dim=-1) - dl,
+            2.0 ** -16 * (prod.abs().sum(dim=-1) + dl.abs()))
+
+
+def attn_bounds(ref, q, k, v, dout, scale):
+    """Per-element rounding bounds of the kernels' results against
+    attn_ref, u = 2^-8.  The kernels round P once (operand of the PV and dV
+    MFMAs), round dS once, round every stored output once and take delta
+    from the bf16 out; everything else is fp32.
+
+    out  : u (Pd |V|) + u |out|
+    dv   : u (Pd^T |dout|) + u |dv|
+    dS   : scale P (u rowsum(|dout| o |out|)) + u |dS|   (delta, then dS)
+    dq   : E_dS |K| + u |dq|;  dk : E_dS^T |Q| + u |dk|
+    lse  : 2^-16 (1 + max_j A_ij), A = scale |Q| |K|^T: a d-term fp32
+           dot product is off by at most d 2^-24 A (d <= 128), the rest is
+           the argument rounding of __expf / __logf, with margin
+    delta: see attn_delta_ref
+    """
+    u = U_BF16
+    p, pd = ref["P"], ref["Pd"]
+    e_out = u * torch.matmul(pd, v.abs()) + u * ref["out"].abs()
+    e_dv = (u * torch.matmul(pd.transpose(-1, -2), dout.abs()) +
+            u * ref["dv"].abs())
+    rs = (dout.abs() * ref["out"].abs()).sum(dim=-1, keepdim=True)
+    e_ds = scale * p * (u * rs) + u * ref["dS"].abs()
+    e_dq = torch.matmul(e_ds, k.abs()) + u * ref["dq"].abs()
+    e_dk = torch.matmul(e_ds.transpose(-1, -2), q.abs()) + u * ref["dk"].abs()
+    a = scale * torch.matmul(q.abs(), k.abs().transpose(-1, -2))
+    a = a.masked_fill(~ref["valid"], 0.0)
+    e_lse = 2.0 ** -16 * (1.0 + a.max(dim=-1).values)
+    _, e_delta = attn_delta_ref(dout, ref["out"], ref["dlse"])
+    return dict(out=e_out, lse=e_lse, delta=e_delta, dq=e_dq, dk=e_dk,
+                dv=e_dv)
+
+
+def attn_emulate(q, k, v, dout, causal, scale, keep=None, inv_keep=1.0,
+                 dlse=None):
+    """attn_ref's arithmetic with the kernels' bf16 roundings inserted:
+    the forward rounds exp(s - max) * keep * inv_keep before the PV product
+    and normalises after it, the backward rounds P * keep * inv_keep (dV)
+    and dS, every stored output is rounded, delta comes from the rounded
+    out.  delta_from is that out, for attn_delta_ref."""
+    valid = attn_valid(q.shape[-2], k.shape[-2], causal)
+    s = torch.matmul(q, k.transpose(-1, -2)) * scale
+    sm = s.masked_fill(~valid, float("-inf"))
+    mx = sm.max(dim=-1, keepdim=True).values
+    e = torch.exp(sm - mx)
+    l = e.sum(dim=-1, keepdim=True)
+    lse = (mx + l.log()).squeeze(-1)
+    kf = 1.0 if keep is None else keep * inv_keep
+    out = bf16_round(torch.matmul(bf16_round(e * kf), v) / l)
+    dl = torch.zeros_like(lse) if dlse is None else dlse
+    delta = (dout * out).sum(dim=-1) - dl
+    p = torch.exp(sm - lse.unsqueeze(-1))
+    pd = bf16_round(p * kf)
+    dp = torch.matmul(dout, v.transpose(-1, -2)) * kf
+    ds = bf16_round(p * (dp - delta.unsqueeze(-1)) * scale)
+    return dict(out=out, lse=lse, delta=delta, delta_from=out,
+                dq=bf16_round(torch.matmul(ds, k)),
+                dk=bf16_round(torch.matmul(ds.transpose(-1, -2), q)),
+                dv=bf16_round(torch.matmul(pd.transpose(-1, -2), dout)))
+
+
+def attn_peak_pairs(seq, causal):
+    """(query row, dominating key) pairs of the ``peaked`` family: every
+    key of ATTN_PEAK_KEYS below seq and key seq-1, each on a row of its
+    own (at or below the diagonal when causal); causal adds rows peaked on
+    their diagonal and on the key before it."""
+    keys = [j for j in ATTN_PEAK_KEYS if j < seq - 1] + [seq - 1]
+    pairs, used = [], set()
+
+    def place(row_candidates, key):
+        for r in row_candidates:
+            if 0 <= r < seq and r not in used and (not causal or r >= key):
+                used.add(r)
+                pairs.append((r, key))
+                return
+
+    for t, j in enumerate(reversed(keys)):
+        # key seq-1 first (causal: only row seq-1 sees it), then rows
+        # spread downwards over the sequence
+        place(list(range(seq - 1 - 3 * t, -1, -1)) +
+              list(range(seq - 1, -1, -1)), j)
+    if causal:
+        for r in (seq // 2, seq // 3, 1):
+            place([r], r)
+        for r in (seq // 2 + 1, seq // 3 + 1, 2):
+            if r >= 1:
+                place([r], r - 1)
+    return pairs
+
+
+def attn_inputs(family, seq, d, causal=False, seed=0, b=ATTN_B, h=ATTN_H):
+    """q, k, v, dout: fp64 [b,h,seq,d] holding bf16-representable values,
+    from a seeded generator.
+
+    randn   : standard normal.
+    peaked  : q, k scaled so max |s| is about 40 (single keys dominate
+              rows), plus the steered rows of attn_peak_pairs with
+              s = 40 on the chosen key.
+    shifted : a unit direction w added as +-c w to q rows (sign by row)
+              and +c w to k, c^2 scale = 60: every score of a row carries a
+              common offset of about +-60, differences stay O(1).
+    """
+    assert family in ATTN_FAMILIES
+    gen = torch.Generator().manual_seed(
+        seed + 1000 * ATTN_FAMILIES.index(family) + 7 * seq + d +
+        (500 if causal else 0))
+    scale = 1.0 / math.sqrt(d)
+    q, k, v, dout = (torch.randn(b, h, seq, d, generator=gen, dtype=F64)
+                     for _ in range(4))
+    if family == "peaked":
+        smax = (torch.matmul(q, k.transpose(-1, -2)) * scale).abs().max()
+        f = math.sqrt(40.0 / smax.item())
+        q, k = q * f, bf16_round(k * f)
+        for row, key in attn_peak_pairs(seq, causal):
+            kj = k[:, :, key]
+            q[:, :, row] = kj * (40.0 / (scale * (kj * kj).sum(
+                dim=-1, keepdim=True)))
+    elif family == "shifted":
+        w = torch.randn(b, h, 1, d, generator=gen, dtype=F64)
+        w = w / w.norm(dim=-1, keepdim=True)
+        c = math.sqrt(60.0 / scale)
+        sign = torch.where((torch.arange(seq) // 2) % 2 == 0, 1.0, -1.0)
+        q = q + c * sign.to(F64)[None, None, :, None] * w
+        k = k + c * w
+    return bf16_round(q), bf16_round(k), bf16_round(v), bf16_round(dout)
+
+
+def attn_dlse(seq, seed=0, b=ATTN_B, h=ATTN_H):
+    """a non-zero cotangent of lse, fp32-representable, fp64 [b,h,seq]"""
+    gen = torch.Generator().manual_seed(4242 + seed + seq)
+    return torch.randn(b, h, seq, generator=gen).to(F64)
+
+
+def unpack_keep(mask_words, bh, seq):
+    """keep bits [bh, seq, seq] (fp64 0/1) from the forward's published
+    int32 mask words [bh * seq * ceil(seq/32)]: bit kv & 31 of word
+    kv >> 5 of row q"""
+    words = mask_words.reshape(bh, seq, (seq + 31) // 32).to(torch.int64)
+    shifts = torch.arange(32, device=words.device)
+    bits = ((words.unsqueeze(-1) >> shifts) & 1).reshape(bh, seq, -1)
+    return bits[:, :, :seq].to(F64)
+
+
+class GuardedBuffer:
+    """A flat device buffer pre-filled with a sentinel bit pattern, a
+    strided view into it behind ``guard`` leading elements, and the map of
+    the elements that view addresses."""
+
+    def __init__(self, shape, strides, offset, dtype, device, guard):
+        sentinel, idt = {
+            2: (ATTN_SENTINEL16, torch.int16),
+            4: (ATTN_SENTINEL32, torch.int32)}[dtype.itemsize]
+        if sentinel >= 2 ** (8 * dtype.itemsize - 1):
+            sentinel -= 2 ** (8 * dtype.itemsize)
+        offset += guard
+        extent = offset + 1 + sum(
+            (n - 1) * st for n, st in zip(shape, strides))
+        self.sentinel = sentinel
+        self.raw = torch.full((extent + guard,), sentinel, dtype=idt,
+                              device=device)
+        self.view = self.raw.view(dtype).as_strided(shape, strides, offset)
+        self.addressed = torch.zeros(extent + guard, dtype=torch.bool)
+        self.addressed.as_strided(shape, strides, offset).fill_(True)
+
+        self.guard = guard
+
+    def sub(self, shape, strides, offset):
+        """a strided view of addressed elements only (the qkv slices)"""
+        offset += self.guard
+        assert bool(self.addressed.as_strided(shape, strides, offset).all())
+        return self.raw.view(self.view.dtype).as_strided(
+            shape, strides, offset)
+
+    def stray_writes(self):
+        """number of unaddressed elements that lost the sentinel"""
+        raw = self.raw.cpu()
+        return int(((raw != self.sentinel) & ~self.addressed).sum())
+
+
+def attn_flat(n, dtype, device, guard=64):
+    """guarded contiguous [n] buffer (lse, delta, mask words)"""
+    return GuardedBuffer((n,), (1,), 0, dtype, device, guard)
+
+
+def attn_layout(name, b, h, seq, d, device, dtype=torch.bfloat16):
+    """Views q, k, v, out, dout, dq, dk, dv (all [b,h,seq,d]) and their
+    GuardedBuffers (``buffers``: name -> buffer), every element pre-filled
+    with the sentinel and two rows of guard on either side.
+
+    plain : q/k/v/dout/grads contiguous [b,h,seq,d]; out in [b,seq,h,d]
+            memory order.
+    qkv   : q/k/v slices of one [b,seq,3,h,d] buffer, the gradients slices
+            of one d_qkv buffer, out and dout in [b,seq,h,d] order.
+    padded: inputs with row stride d+8 at storage offset 8, out
+            contiguous [b,h,seq,d], dout a permuted [b,seq,h,d] view, the
+            gradients with row stride d+16 at storage offset 16: the four
+            stride triplets differ.
+    """
+    shape = (b, h, seq, d)
+    guard = 2 * (d + 16)
+    bhsd = (h * seq * d, seq * d, d, 1)
+    bshd = (seq * h * d, d, h * d, 1)
+    bufs, views = {}, {}
+
+    def own(key, strides, offset=0):
+        bufs[key] = GuardedBuffer(shape, strides, offset, dtype, device,
+                                  guard)
+        views[key] = bufs[key].view
+
+    if name == "plain":
+        for key in ("q", "k", "v", "dout", "dq", "dk", "dv"):
+            own(key, bhsd)
+        own("out", bshd)
+    elif name == "qkv":
+        packed = (seq * 3 * h * d, d, 3 * h * d, 1)
+        for buf_key, keys in (("qkv", ("q", "k", "v")),
+                              ("d_qkv", ("dq", "dk", "dv"))):
+            bufs[buf_key] = GuardedBuffer(
+                (b, seq, 3, h, d),
+                (seq * 3 * h * d, 3 * h * d, h * d, d, 1), 0, dtype,
+                device, guard)
+            for i, key in enumerate(keys):
+                views[key] = bufs[buf_key].sub(shape, packed, i * h * d)
+        own("out", bshd)
+        own("dout", bshd)
+    elif name == "padded":
+        pin = (h * seq * (d + 8), seq * (d + 8), d + 8, 1)
+        pg = (h * seq * (d + 16), seq * (d + 16), d + 16, 1)
+        for key in ("q", "k", "v"):
+            own(key, pin, 8)
+        for key in ("dq", "dk", "dv"):
+            own(key, pg, 16)
+        own("out", bhsd)
+        own("dout", bshd)
+    else:
+        raise ValueError(name)
+    views["buffers"] = bufs
+    return views

@@ -245,3 +245,299 @@ def test_moe_backward_refs_are_the_adjoints():
     assert torch.allclose(dh, h.grad, rtol=1e-12, atol=1e-14)
     assert torch.allclose(dfw, fwd.grad, rtol=1e-12, atol=1e-14)
     assert (dfw[~keep] == 0).all()
+
+
+# ---- flash attention ---------------------------------------------------------
+def _cpu_keep(seq, thresh, seed=0):
+    """Bernoulli keep bits at the kernel's rate 1 - thresh/256"""
+    if not thresh:
+        return None
+    gen = torch.Generator().manual_seed(900 + seed + seq + thresh)
+    u = torch.rand(kr.ATTN_B, kr.ATTN_H, seq, seq, generator=gen, dtype=F64)
+    return (u >= thresh / 256.0).to(F64)
+
+
+def _attn_case(family, seq, d, causal, thresh=0, with_dlse=False):
+    q, k, v, dout = kr.attn_inputs(family, seq, d, causal)
+    keep = _cpu_keep(seq, thresh)
+    dlse = kr.attn_dlse(seq) if with_dlse else None
+    return q, k, v, dout, d ** -0.5, keep, kr.attn_inv_keep(thresh), dlse
+
+
+def _rel(a, b):
+    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-300))
+
+
+@pytest.mark.parametrize("family", kr.ATTN_FAMILIES)
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("thresh,with_dlse", [(0, False), (128, True)])
+def test_attn_ref_matches_autograd(family, causal, thresh, with_dlse):
+    for seq, d in ((1, 64), (33, 128), (72, 64), (129, 64)):
+        q, k, v, dout, scale, keep, inv_keep, dlse = _attn_case(
+            family, seq, d, causal, thresh, with_dlse)
+        ref = kr.attn_ref(q, k, v, dout, causal, scale, keep, inv_keep,
+                          dlse)
+        qa, ka, va = (t.clone().requires_grad_(True) for t in (q, k, v))
+        s = torch.matmul(qa, ka.transpose(-1, -2)) * scale
+        if causal:
+            s = s.masked_fill(torch.triu(torch.ones(
+                seq, seq, dtype=torch.bool), 1), float("-inf"))
+        p = torch.softmax(s, dim=-1)
+        if keep is not None:
+            p = p * keep * inv_keep
+        out = torch.matmul(p, va)
+        lse = torch.logsumexp(s, dim=-1)
+        dl = dlse if dlse is not None else torch.zeros_like(lse)
+        gq, gk, gv = torch.autograd.grad([out, lse], [qa, ka, va],
+                                         [dout, dl])
+        for name, want in (("out", out.detach()), ("lse", lse.detach()),
+                           ("dq", gq), ("dk", gk), ("dv", gv)):
+            assert _rel(ref[name], want) < 1e-12, (name, seq, d)
+        if keep is None:
+            sdpa = torch.nn.functional.scaled_dot_product_attention(
+                q, k, v, is_causal=causal, scale=scale)
+            assert _rel(ref["out"], sdpa) < 1e-12, (seq, d)
+
+
+def test_attn_input_families_have_their_properties():
+    for d in kr.ATTN_DIMS:
+        for seq in (72, 200, 257):
+            for causal in (False, True):
+                scale = d ** -0.5
+                for family in kr.ATTN_FAMILIES:
+                    ts = kr.attn_inputs(family, seq, d, causal)
+                    for t in ts:     # exactly representable in bf16
+                        assert t.shape == (kr.ATTN_B, kr.ATTN_H, seq, d)
+                        assert torch.equal(kr.bf16_round(t), t)
+                    again = kr.attn_inputs(family, seq, d, causal)
+                    assert all(torch.equal(a, b) for a, b in zip(ts, again))
+                q, k, v, dout = kr.attn_inputs("peaked", seq, d, causal)
+                ref = kr.attn_ref(q, k, v, dout, causal, scale)
+                assert 30 < float(ref["s"].abs().max()) < 60
+                pairs = kr.attn_peak_pairs(seq, causal)
+                keys = {key for _, key in pairs}
+                assert keys >= {0, 31, 32, 63, 64, seq - 1}
+                assert (127 in keys and 128 in keys) or seq <= 128
+                if causal:
+                    assert any(r == key for r, key in pairs)
+                    assert any(r == key + 1 for r, key in pairs)
+                for row, key in pairs:
+                    assert not causal or key <= row
+                    assert float(ref["P"][:, :, row, key].min()) > 0.9
+                q, k, v, dout = kr.attn_inputs("shifted", seq, d, causal)
+                s = kr.attn_ref(q, k, v, dout, False, scale)["s"]
+                mean = s.mean(dim=-1)
+                assert float(mean.max()) > 50 and float(mean.min()) < -50
+                assert float(mean.abs().min()) > 40
+                assert float(s.std(dim=-1).max()) < 6
+
+
+def _emulation_ratios(case):
+    q, k, v, dout, scale, keep, inv_keep, dlse = case[:8]
+    causal = case[8]
+    ref = kr.attn_ref(q, k, v, dout, causal, scale, keep, inv_keep, dlse)
+    bounds = kr.attn_bounds(ref, q, k, v, dout, scale)
+    emu = kr.attn_emulate(q, k, v, dout, causal, scale, keep, inv_keep, dlse)
+    ratios = {}
+    for name in kr.ATTN_OUTPUTS:
+        want, bound = ref[name], bounds[name]
+        if name == "delta":
+            want, bound = kr.attn_delta_ref(dout, emu["delta_from"], dlse)
+        ratios[name] = kr.attn_ratio((emu[name] - want).abs(), bound)
+    return ratios
+
+
+def _assert_emulation_inside(label, case, worst):
+    for name, r in _emulation_ratios(case).items():
+        worst[name] = max(worst.get(name, 0.0), r)
+        assert r <= 1.0, (label, name, r)
+
+
+@pytest.mark.parametrize("family", kr.ATTN_FAMILIES)
+@pytest.mark.parametrize("d", kr.ATTN_DIMS)
+@pytest.mark.parametrize("causal", [False, True])
+def test_attn_emulation_inside_bounds_main(family, d, causal):
+    worst = {}
+    for seq in kr.ATTN_SEQS:
+        _assert_emulation_inside(
+            (seq,), _attn_case(family, seq, d, causal) + (causal,), worst)
+    print(family, d, causal, worst)
+
+
+@pytest.mark.parametrize("thresh", sorted(kr.ATTN_DROP_FAMILY))
+@pytest.mark.parametrize("d", kr.ATTN_DIMS)
+@pytest.mark.parametrize("causal", [False, True])
+def test_attn_emulation_inside_bounds_dropout(thresh, d, causal):
+    worst = {}
+    # threshold 128 also runs on randn (the garbage-bit test)
+    families = kr.ATTN_FAMILIES if thresh == 128 else (
+        kr.ATTN_DROP_FAMILY[thresh],)
+    for seq in kr.ATTN_DROP_SEQS:
+        for family in families:
+            _assert_emulation_inside(
+                (seq, family), _attn_case(family, seq, d, causal, thresh) +
+                (causal,), worst)
+    print(thresh, d, causal, worst)
+
+
+@pytest.mark.parametrize("d", kr.ATTN_DIMS)
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("thresh", [0, 128])
+def test_attn_emulation_inside_bounds_dlse(d, causal, thresh):
+    worst = {}
+    for seq in kr.ATTN_DLSE_SEQS:
+        for family in kr.ATTN_FAMILIES:
+            _assert_emulation_inside(
+                (seq, family), _attn_case(family, seq, d, causal, thresh,
+                                          True) + (causal,), worst)
+    print(d, causal, thresh, worst)
+
+
+def test_attn_emulation_inside_bounds_env_cases():
+    worst = {}
+    for d, seq, causal, thresh, family in kr.attn_env_cases(0):
+        _assert_emulation_inside(
+            (d, seq, causal, thresh, family),
+            _attn_case(family, seq, d, causal, thresh) + (causal,), worst)
+    print(worst)
+
+
+ATTN_MUTATIONS = (
+    "causal_ge", "last_key_dropped", "padding_key_counted",
+    "v_rows_exchanged", "bh_transposed", "keep_from_neighbour_key",
+    "dp_without_inv_keep", "dropout_in_normaliser", "dlse_dropped",
+    "dlse_negated", "lse_without_last_tile")
+
+
+def _attn_mutants(q, k, v, dout, causal, scale, keep, inv_keep, dlse, ref):
+    """wrong kernels, as outputs of a mutated reference: name -> outputs"""
+    b, h, seq, _ = q.shape
+    kt = lambda t: t.transpose(-1, -2)
+    m = {}
+    if causal:
+        # masks kv >= q instead of kv > q; row 0 keeps its only key
+        valid = torch.tril(torch.ones(seq, seq, dtype=torch.bool), -1)
+        valid[0, 0] = True
+        m["causal_ge"] = kr.attn_ref(q, k, v, dout, causal, scale, keep,
+                                     inv_keep, dlse, valid=valid)
+    valid = ref["valid"].clone()
+    valid[:, seq - 1] = False
+    m["last_key_dropped"] = kr.attn_ref(q, k, v, dout, causal, scale, keep,
+                                        inv_keep, dlse, valid=valid)
+    if not causal:
+        ext = lambda t, dim: torch.cat(
+            [t, t.narrow(dim, t.shape[dim] - 1, 1)], dim)
+        r = kr.attn_ref(q, ext(k, 2), ext(v, 2), dout, False, scale,
+                        None if keep is None else ext(keep, 3), inv_keep,
+                        dlse)
+        m["padding_key_counted"] = dict(
+            r, dk=r["dk"][:, :, :seq], dv=r["dv"][:, :, :seq])
+    j = seq // 2
+    v2 = v.clone()
+    v2[:, :, [j, j + 1]] = v[:, :, [j + 1, j]]
+    m["v_rows_exchanged"] = kr.attn_ref(q, k, v2, dout, causal, scale, keep,
+                                        inv_keep, dlse)
+    idx = [(bh % b) * h + bh // b for bh in range(b * h)]
+    fl = lambda t: t.reshape(b * h, seq, -1)[idx].reshape(t.shape)
+    m["bh_transposed"] = kr.attn_ref(fl(q), fl(k), fl(v), fl(dout), causal,
+                                     scale, keep, inv_keep, dlse)
+    if keep is not None:
+        m["keep_from_neighbour_key"] = kr.attn_ref(
+            q, k, v, dout, causal, scale, torch.roll(keep, 1, -1), inv_keep,
+            dlse)
+        dp = torch.matmul(dout, kt(v)) * keep
+        ds = ref["P"] * (dp - ref["delta"].unsqueeze(-1)) * scale
+        m["dp_without_inv_keep"] = dict(dq=torch.matmul(ds, k),
+                                        dk=torch.matmul(kt(ds), q))
+        e = ref["P"] * keep
+        m["dropout_in_normaliser"] = dict(out=torch.matmul(
+            e / e.sum(dim=-1, keepdim=True).clamp_min(1e-300), v))
+    if dlse is not None:
+        m["dlse_dropped"] = kr.attn_ref(q, k, v, dout, causal, scale, keep,
+                                        inv_keep, None)
+        m["dlse_negated"] = kr.attn_ref(q, k, v, dout, causal, scale, keep,
+                                        inv_keep, -dlse)
+    if seq > 64:
+        valid = ref["valid"].clone()
+        valid[:, (seq - 1) // 64 * 64:] = False
+        m["lse_without_last_tile"] = dict(lse=kr.attn_ref(
+            q, k, v, dout, causal, scale, valid=valid)["lse"])
+    return m
+
+
+@pytest.fixture(scope="module")
+def attn_mutation_ratios():
+    """{mutation: {case label: worst err / (factor * E)}} over a slice of
+    the GPU matrix"""
+    res = {name: {} for name in ATTN_MUTATIONS}
+    for family in kr.ATTN_FAMILIES:
+        for seq, d in ((72, 64), (200, 64), (257, 128)):
+            for causal in (False, True):
+                for thresh, with_dlse in ((0, False), (128, True)):
+                    case = _attn_case(family, seq, d, causal, thresh,
+                                      with_dlse)
+                    q, k, v, dout, scale, keep, inv_keep, dlse = case
+                    ref = kr.attn_ref(q, k, v, dout, causal, scale, keep,
+                                      inv_keep, dlse)
+                    bounds = kr.attn_bounds(ref, q, k, v, dout, scale)
+                    label = (family, seq, d, causal, thresh)
+                    for name, outs in _attn_mutants(
+                            *case[:4], causal, *case[4:], ref).items():
+                        res[name][label] = max(
+                            kr.attn_ratio((outs[o] - ref[o]).abs(),
+                                          kr.ATTN_FACTOR[o] * bounds[o])
+                            for o in ("out", "lse", "dq", "dk", "dv")
+                            if o in outs)
+    return res
+
+
+@pytest.mark.parametrize("mutation", ATTN_MUTATIONS)
+def test_attn_bounds_reject_mutation(attn_mutation_ratios, mutation):
+    ratios = attn_mutation_ratios[mutation]
+    assert ratios, mutation
+    best = max(ratios, key=ratios.get)
+    print(mutation, "worst err / allowed:", ratios[best], "at", best,
+          "; weakest case:", min(ratios.values()))
+    assert ratios[best] >= 10.0, (mutation, best, ratios[best])
+
+
+def test_attn_layouts_and_unpack_keep():
+    b, h, seq, d = kr.ATTN_B, kr.ATTN_H, 5, 64
+    triplets = {}
+    for name in kr.ATTN_LAYOUTS:
+        lay = kr.attn_layout(name, b, h, seq, d, "cpu")
+        for key in ("q", "k", "v", "out", "dout", "dq", "dk", "dv"):
+            t = lay[key]
+            assert t.shape == (b, h, seq, d) and t.stride(3) == 1
+            assert t.stride(1) % 8 == 0 and t.stride(2) % 8 == 0
+            assert t.storage_offset() % 8 == 0
+            assert bool(torch.isnan(t.float()).all())    # sentinel
+        assert lay["q"].stride() == lay["k"].stride() == lay["v"].stride()
+        assert lay["dq"].stride() == lay["dk"].stride() == lay["dv"].stride()
+        triplets[name] = [lay[key].stride()[:3]
+                          for key in ("q", "out", "dout", "dq")]
+        # a write through the views leaves the sentinels, one outside
+        # them is noticed
+        for key in ("out", "dq", "dk", "dv"):
+            lay[key].fill_(1.0)
+        assert all(buf.stray_writes() == 0
+                   for buf in lay["buffers"].values())
+        for buf in lay["buffers"].values():
+            assert not bool(buf.addressed[:buf.guard].any())
+            assert not bool(buf.addressed[-buf.guard:].any())
+        victim = lay["buffers"]["out"]
+        victim.raw[0] = 0
+        assert victim.stray_writes() == 1
+    assert len(set(triplets["padded"])) == 4
+    assert lay["buffers"]["dq"].raw.numel() > b * h * seq * (d + 16)
+
+    words = torch.tensor([0b101, -1, -2 ** 31, 0, 6, 7], dtype=torch.int32)
+    keep = kr.unpack_keep(words, 2, 3)
+    assert keep.tolist() == [[[1, 0, 1], [1, 1, 1], [0, 0, 0]],
+                             [[0, 0, 0], [0, 1, 1], [1, 1, 1]]]
+    gen = torch.Generator().manual_seed(3)
+    bits = torch.randint(0, 2, (2, 40, 64), generator=gen)
+    packed = (bits.reshape(2, 40, 2, 32) << torch.arange(32)).sum(-1)
+    packed = torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed)
+    keep = kr.unpack_keep(packed.to(torch.int32).reshape(-1), 2, 40)
+    assert torch.equal(keep, bits[:, :, :40].to(F64))
