@@ -249,6 +249,9 @@ __global__ void lamb_phase2_kernel(float* __restrict__ master,
 // With HAS_RES the summed input s is also written out (the tensor the
 // backward normalizes against and, for pre-LN blocks, the residual
 // stream).  Saves mean and rstd.
+// Statistics in two passes over the cached row: mean = p + sum(s - p) / n
+// around a pivot p, then var = sum((s - mean)^2) / n.  (sumsq / n - mean^2
+// cancels in fp32 on rows with an offset: NaN on near-constant rows.)
 // ============================================================================
 template <bool HAS_RES, int CHUNKS>
 __global__ void layer_norm_fwd_bf16_kernel(
@@ -271,7 +274,12 @@ __global__ void layer_norm_fwd_bf16_kernel(
   }
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const int64_t base = row * cols;
-    float sum = 0.f, sumsq = 0.f;
+    // pivot: the row's first element, read by every thread (one broadcast
+    // load).  Summing s - pivot keeps the fp32 error of the mean
+    // proportional to the row's spread, not to its offset.
+    float piv = bf2f(reinterpret_cast<const T*>(x)[base]);
+    if (HAS_RES) piv += bf2f(reinterpret_cast<const T*>(res)[base]);
+    float sum = 0.f;
 #pragma unroll
     for (int k = 0; k < CHUNKS; ++k) {
       const int64_t c = ((int64_t)threadIdx.x + k * blockDim.x) * 8;
@@ -285,17 +293,26 @@ __global__ void layer_norm_fwd_bf16_kernel(
       }
       cache[k] = f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        sum += f.v[j];
-        sumsq += f.v[j] * f.v[j];
-      }
+      for (int j = 0; j < 8; ++j) sum += f.v[j] - piv;
     }
     sum = block_reduce_sum(sum, lds);
+    const float mean = piv + sum / cols;
+    // variance as the mean of squared deviations from that mean, out of
+    // the cached row: all addends are >= 0, nothing cancels
+    float ssq = 0.f;
+#pragma unroll
+    for (int k = 0; k < CHUNKS; ++k) {
+      const int64_t c = ((int64_t)threadIdx.x + k * blockDim.x) * 8;
+      if (c >= cols) continue;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = cache[k].v[j] - mean;
+        ssq += d * d;
+      }
+    }
     __syncthreads();
-    sumsq = block_reduce_sum(sumsq, lds);
-    const float mean = sum / cols;
-    const float var = sumsq / cols - mean * mean;
-    const float rstd = rsqrtf(var + eps);
+    ssq = block_reduce_sum(ssq, lds);
+    const float rstd = rsqrtf(ssq / cols + eps);
     if (threadIdx.x == 0) {
       mean_out[row] = mean;
       rstd_out[row] = rstd;
@@ -314,7 +331,8 @@ __global__ void layer_norm_fwd_bf16_kernel(
   }
 }
 
-// generic (fp32 / large-cols) forward: two-pass re-read
+// generic (fp32 / large-cols) forward: re-reads the row for the variance
+// and for the normalize pass
 template <bool BF16, bool HAS_RES>
 __global__ void layer_norm_fwd_kernel(
     void* __restrict__ out, const void* __restrict__ x,
@@ -326,27 +344,40 @@ __global__ void layer_norm_fwd_kernel(
   using T = unsigned short;
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const int64_t base = row * cols;
-    float sum = 0.f, sumsq = 0.f;
+    // s = x (+ res) in fp32, before any rounding of the stored sum
+    auto s_at = [&](int64_t i) -> float {
+      float fv = BF16 ? bf2f(reinterpret_cast<const T*>(x)[i])
+                      : reinterpret_cast<const float*>(x)[i];
+      if (HAS_RES)
+        fv += BF16 ? bf2f(reinterpret_cast<const T*>(res)[i])
+                   : reinterpret_cast<const float*>(res)[i];
+      return fv;
+    };
+    const float piv = s_at(base);   // pivot, as in the fast kernel
+    float sum = 0.f;
     for (int64_t c = threadIdx.x; c < cols; c += blockDim.x) {
-      float fv = BF16 ? bf2f(reinterpret_cast<const T*>(x)[base + c])
-                      : reinterpret_cast<const float*>(x)[base + c];
+      const float fv = s_at(base + c);
       if (HAS_RES) {
-        fv += BF16 ? bf2f(reinterpret_cast<const T*>(res)[base + c])
-                   : reinterpret_cast<const float*>(res)[base + c];
         if (BF16)
           reinterpret_cast<T*>(sum_out)[base + c] = f2bf(fv);
         else
           reinterpret_cast<float*>(sum_out)[base + c] = fv;
       }
-      sum += fv;
-      sumsq += fv * fv;
+      sum += fv - piv;
     }
     sum = block_reduce_sum(sum, lds);
+    const float mean = piv + sum / cols;
+    // second read of the row (L2-resident) for the squared deviations: a
+    // shifted two-moment form would still cancel when the pivot is the
+    // row's outlier
+    float ssq = 0.f;
+    for (int64_t c = threadIdx.x; c < cols; c += blockDim.x) {
+      const float d = s_at(base + c) - mean;
+      ssq += d * d;
+    }
     __syncthreads();
-    sumsq = block_reduce_sum(sumsq, lds);
-    const float mean = sum / cols;
-    const float var = sumsq / cols - mean * mean;
-    const float rstd = rsqrtf(var + eps);
+    ssq = block_reduce_sum(ssq, lds);
+    const float rstd = rsqrtf(ssq / cols + eps);
     if (threadIdx.x == 0) {
       mean_out[row] = mean;
       rstd_out[row] = rstd;

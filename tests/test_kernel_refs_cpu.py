@@ -541,3 +541,327 @@ def test_attn_layouts_and_unpack_keep():
     packed = torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed)
     keep = kr.unpack_keep(packed.to(torch.int32).reshape(-1), 2, 40)
     assert torch.equal(keep, bits[:, :, :40].to(F64))
+
+
+# ---- LayerNorm, bias + GeLU, column sum -------------------------------------
+def _close(a, b):
+    return float((a - b).abs().max()) <= 1e-12 * max(
+        1.0, float(b.abs().max()))
+
+
+@pytest.mark.parametrize("with_res", [False, True])
+@pytest.mark.parametrize("rows,cols", [(1, 8), (37, 520), (37, 1000)])
+def test_ln_ref_matches_torch(rows, cols, with_res):
+    inp = kr.ln_inputs(rows, cols, with_res, dy_name="cancel")
+    ref = kr.ln_ref(inp["x"], inp["res"], inp["gamma"], inp["beta"])
+    s = inp["x"] if not with_res else inp["x"] + inp["res"]
+    sa = s.clone().requires_grad_(True)
+    ga = inp["gamma"].clone().requires_grad_(True)
+    ba = inp["beta"].clone().requires_grad_(True)
+    out = torch.nn.functional.layer_norm(sa, (cols,), ga, ba, kr.LN_EPS)
+    assert _close(ref["out"], out.detach())
+    assert _close(ref["mean"], s.mean(1))
+    assert _close(ref["rstd"], (s.var(1, unbiased=False) + kr.LN_EPS) ** -0.5)
+    out.backward(inp["dy"])
+    bwd = kr.ln_bwd_ref(inp["dy"], s, inp["gamma"], ref["mean"],
+                        ref["rstd"], inp["dadd"])
+    # autograd's dx of a constant row is 0 * rstd: scale by the largest
+    scale = max(1.0, float(sa.grad.abs().max()))
+    assert float((bwd["dx_ln"] - sa.grad).abs().max()) <= 1e-12 * scale
+    assert _close(bwd["dx"], sa.grad + inp["dadd"])
+    assert _close(bwd["dgamma"], ga.grad)
+    assert _close(bwd["dbeta"], ba.grad)
+    assert _close(bwd["colsum"], (sa.grad + inp["dadd"]).sum(0))
+    assert _close(kr.colsum_ref(inp["dy"]), inp["dy"].sum(0))
+
+
+def test_bias_gelu_ref_matches_torch():
+    inp = kr.bias_gelu_inputs(37, 520)
+    ref = kr.bias_gelu_ref(inp["x"], inp["bias"], inp["dy"])
+    xa = inp["x"].clone().requires_grad_(True)
+    ba = inp["bias"].clone().requires_grad_(True)
+    out = torch.nn.functional.gelu(xa + ba, approximate="tanh")
+    out.backward(inp["dy"])
+    assert _close(ref["out"], out.detach())
+    assert _close(ref["dx"], xa.grad)
+    assert _close(ref["dbias"], ba.grad)
+    # the second derivative's bound used by bias_gelu_bounds
+    z = torch.linspace(-14, 14, 280001, dtype=F64)
+    g = kr.gelu_tanh_grad(z)
+    d2 = (g[2:] - g[:-2]) / (z[2:] - z[:-2])
+    assert 0.79 < float(d2.abs().max()) < kr.GELU_D2_MAX
+
+
+def test_ln_and_gelu_inputs_have_their_properties():
+    nk = len(kr.LN_KINDS)
+    assert {f for _, f, _ in kr.LN_KINDS} == set(kr.LN_FAMILIES)
+    for rows, cols in ((37, 1000), (37, 8), (3, 4096)):
+        for with_res in (False, True):
+            inp = kr.ln_inputs(rows, cols, with_res)
+            for key in ("x", "gamma", "beta", "dy", "dadd"):
+                assert torch.equal(kr.bf16_round(inp[key]), inp[key]), key
+            again = kr.ln_inputs(rows, cols, with_res)
+            assert torch.equal(inp["x"], again["x"])
+            s = inp["x"]
+            if with_res:
+                assert torch.equal(kr.bf16_round(inp["res"]), inp["res"])
+                s = s + inp["res"]
+                assert float(inp["res"].abs().max()) > 0
+            ref = kr.ln_ref(inp["x"], inp["res"], inp["gamma"], inp["beta"])
+            assert float(inp["gamma"][cols // 3]) == 0
+            assert float(inp["gamma"][cols - 1]) < 0
+            for r in range(rows):
+                name, family, par = kr.LN_KINDS[int(inp["kinds"][r])]
+                row = s[r]
+                if family != "randn":       # the sum is representable
+                    assert torch.equal(kr.bf16_round(row), row), name
+                if family == "const":
+                    assert float(row.max()) == float(row.min())
+                    assert abs(float(row[0]) - par) <= 2.0 ** -8 * abs(par)
+                    assert float((ref["out"][r] - inp["beta"]).abs().max()) \
+                        < 1e-9
+                    assert abs(float(ref["rstd"][r]) * kr.LN_EPS ** 0.5 - 1) \
+                        < 1e-12
+                if family == "near_const":
+                    base, step, m = par
+                    m = max(1, min(m, cols // 2))
+                    assert int((row == base).sum()) == cols - m
+                    assert int((row == base + step).sum()) == m
+                    assert float(kr.bf16_round(torch.tensor(
+                        base + step / 2, dtype=F64))) in (base, base + step)
+                if family == "offset":
+                    assert abs(float(row.mean()) - par[1]) < par[0]
+                if family == "tiny":
+                    assert float(ref["var"][r]) < 1e-3 * kr.LN_EPS
+                if family == "one_hot":
+                    assert int((row != 0).sum()) == 1 and \
+                        float(row.max()) == 1000.0
+    for rows in (1, 3, 37):
+        seen = set()
+        for rot in kr.ln_rots(rows):
+            seen |= set(kr.ln_row_kinds(rows, rot).tolist())
+        assert seen == set(range(nk))
+    gen = torch.Generator().manual_seed(0)
+    co = kr.dy_family("coherent", 37, 24, gen)
+    ca = kr.dy_family("cancel", 37, 24, gen)
+    assert torch.equal(co.sum(0).abs(), co.abs().sum(0))
+    assert torch.equal(ca[:36].sum(0), torch.zeros(24, dtype=F64))
+    assert float(ca.abs().sum(0).min()) > 5
+    # the GeLU sweep reaches both saturated ends and the derivative's
+    # minimum, +-40 included, in every shape with room for it
+    for rows, cols in ((1, 8), (3, 24), (37, 512), (1025, 1536)):
+        inp = kr.bias_gelu_inputs(rows, cols)
+        z = (inp["x"] + inp["bias"]).reshape(-1)[:inp["nsweep"]]
+        assert torch.equal(kr.bf16_round(inp["x"]), inp["x"])
+        assert float(z.max()) > 39 and float(z.min()) < -39
+        if rows * cols >= 2 * kr.gelu_sweep().numel():
+            assert float((z[:-2] - kr.gelu_sweep()[:-2]).abs().max()) < 0.07
+            assert bool(((z > -0.8) & (z < -0.7)).any())
+            assert float(z[:-2].min()) < -11.9 and float(z[:-2].max()) > 11.9
+
+
+def _emu_fwd(bf16):
+    return lambda inp, with_res: kr.ln_emulate(
+        inp["x"], inp["res"], inp["gamma"], inp["beta"], bf16)
+
+
+def _emu_bwd(bf16):
+    def fn(inp, x_used, mean, rstd, dadd, want_colsum):
+        return kr.ln_bwd_emulate(inp["dy"], x_used, inp["gamma"], mean, rstd,
+                                 dadd, bf16)
+    return fn
+
+
+@pytest.mark.parametrize("cols,rows,bf16", kr.ln_cases())
+def test_ln_emulation_inside_bounds(cols, rows, bf16):
+    """the rounding model stays within the GPU tests' criterion on every
+    element of every case of the GPU matrix: 1 x E on the fp32 results,
+    2 x E on the bf16 tensors (E carries 2^-9 |ref| for the final
+    rounding, and one correct bf16 rounding alone reaches 2^-8 |ref|).
+    Every rstd bound is within 2^-12 relative, asserted by ln_check_case"""
+    worst, bad = kr.ln_check_case(
+        cols, rows, bf16, _emu_fwd(bf16), _emu_bwd(bf16),
+        kr.LN_FACTOR_BF16 if bf16 else kr.LN_FACTOR_F32)
+    print("LN-EMU cols %d rows %d bf16 %d %s"
+          % (cols, rows, bf16, kr.format_worst(worst)))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("rows,cols,bf16", kr.gelu_cases())
+def test_bias_gelu_emulation_inside_bounds(rows, cols, bf16):
+    worst, bad = kr.gelu_check_case(
+        rows, cols, bf16, lambda inp: kr.bias_gelu_emulate(
+            inp["x"], inp["bias"], inp["dy"], bf16),
+        kr.GELU_FACTOR_BF16 if bf16 else kr.GELU_FACTOR_F32)
+    print("GELU-EMU rows %d cols %d bf16 %d %s"
+          % (rows, cols, bf16, kr.format_worst(worst)))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("bf16", [True, False])
+def test_colsum_emulation_inside_bounds(bf16):
+    for cols in kr.COLSUM_COLS:
+        for rows in kr.COLSUM_ROWS:
+            for name in kr.LN_DY_FAMILIES:
+                gen = torch.Generator().manual_seed(rows + cols)
+                dy = kr.dy_family(name, rows, cols, gen)
+                r = kr.ratio_of(kr.colsum_emulate(dy, bf16),
+                                kr.colsum_ref(dy), kr.colsum_bounds(dy, bf16))
+                assert r <= (2.0 if bf16 else 1.0), (cols, rows, name, r)
+
+
+def test_two_moment_variance_breaks_the_listed_rows():
+    """the parent kernels' var = sumsq / n - mean^2 in fp32 on the rows the
+    issue lists: NaN or an rstd far outside the bound, where the shipped
+    algorithm's emulation is inside it"""
+    f = torch.float32
+    for cols in (1000, 1536, 4096):
+        inp = kr.ln_inputs(37, cols, False)
+        ref = kr.ln_ref(inp["x"], None, inp["gamma"], inp["beta"])
+        e = kr.ln_fwd_bounds(ref, inp["x"], None, inp["gamma"], inp["beta"],
+                             True)
+        x = inp["x"].to(f)
+        mean = x.sum(1) / cols
+        rstd = torch.rsqrt((x * x).sum(1) / cols - mean * mean + kr.LN_EPS)
+        bad = ~((rstd.to(F64) - ref["rstd"]).abs() <= e["rstd"])
+        kinds = {kr.LN_KINDS[int(k)][1] for k in inp["kinds"][bad]}
+        assert {"offset", "near_const"} <= kinds, kinds
+        emu = kr.ln_emulate(inp["x"], None, inp["gamma"], inp["beta"], True)
+        assert bool(((emu["rstd"] - ref["rstd"]).abs() <= e["rstd"]).all())
+
+
+LN_MUTATIONS = (
+    "mean_of_neighbour_row", "rstd_without_eps", "two_moment_variance",
+    "last_vector_outside_stats", "gamma_shifted_8", "beta_dropped",
+    "residual_after_stats", "dx_without_sum_dygx", "dadd_dropped",
+    "dgamma_missing_last_row", "dgamma_partial_twice", "colsum_before_dadd")
+
+
+def _ln_mutants(inp, ref, bwd):
+    """wrong kernels as mutated references: name -> {output: value}"""
+    x, res, gamma, beta = inp["x"], inp["res"], inp["gamma"], inp["beta"]
+    dy, dadd = inp["dy"], inp["dadd"]
+    s, mean, rstd = ref["s"], ref["mean"], ref["rstd"]
+    rows, cols = x.shape
+    m = {}
+
+    def out_at(mu, rs, g=gamma, b=beta):
+        return (s - mu[:, None]) * rs[:, None] * g + b
+
+    if rows > 1:
+        mu = torch.roll(mean, 1)
+        m["mean_of_neighbour_row"] = dict(mean=mu, out=out_at(mu, rstd))
+    rs = ref["var"] ** -0.5
+    m["rstd_without_eps"] = dict(rstd=rs, out=out_at(mean, rs))
+    f = torch.float32
+    s32 = s.to(f)
+    mu32 = s32.sum(1) / cols
+    rs32 = torch.rsqrt((s32 * s32).sum(1) / cols - mu32 * mu32 +
+                       torch.tensor(kr.LN_EPS, dtype=f))
+    m["two_moment_variance"] = dict(
+        mean=mu32.to(F64), rstd=rs32.to(F64),
+        out=out_at(mu32.to(F64), rs32.to(F64)))
+    if cols > 8:
+        part = kr.ln_ref(s[:, :-8], None, gamma[:-8], beta[:-8])
+        m["last_vector_outside_stats"] = dict(
+            mean=part["mean"], rstd=part["rstd"],
+            out=out_at(part["mean"], part["rstd"]))
+        m["gamma_shifted_8"] = dict(
+            out=out_at(mean, rstd, g=torch.roll(gamma, 8)))
+    m["beta_dropped"] = dict(out=out_at(mean, rstd, b=0 * beta))
+    if res is not None:
+        part = kr.ln_ref(x, None, gamma, beta)
+        m["residual_after_stats"] = dict(
+            mean=part["mean"], rstd=part["rstd"],
+            out=out_at(part["mean"], part["rstd"]))
+    m["dx_without_sum_dygx"] = dict(
+        dx=(bwd["dyg"] - bwd["a"] / cols) * rstd[:, None] + dadd)
+    m["dadd_dropped"] = dict(dx=bwd["dx_ln"], colsum=bwd["dx_ln"].sum(0))
+    if rows > 1:
+        m["dgamma_missing_last_row"] = dict(
+            dgamma=bwd["dgamma"] - dy[-1] * bwd["xhat"][-1])
+    own = slice(0, rows, kr.ln_bwd_waves(rows))     # the rows of wave 0
+    m["dgamma_partial_twice"] = dict(
+        dgamma=bwd["dgamma"] + (dy[own] * bwd["xhat"][own]).sum(0))
+    m["colsum_before_dadd"] = dict(colsum=bwd["dx_ln"].sum(0))
+    return m
+
+
+@pytest.fixture(scope="module")
+def ln_mutation_ratios():
+    """{mutation: {case: worst err / (factor x E)}} over a slice of the
+    matrix, backward at the reference statistics with dadd"""
+    out = {name: {} for name in LN_MUTATIONS}
+    for cols, rows in ((64, 3), (520, 37), (1536, 37), (4096, 37)):
+        for with_res in (False, True):
+            for dy_name in kr.LN_DY_FAMILIES:
+                inp = kr.ln_inputs(rows, cols, with_res, dy_name)
+                ref = kr.ln_ref(inp["x"], inp["res"], inp["gamma"],
+                                inp["beta"])
+                e = kr.ln_fwd_bounds(ref, inp["x"], inp["res"], inp["gamma"],
+                                     inp["beta"], True)
+                bwd = kr.ln_bwd_ref(inp["dy"], ref["s"], inp["gamma"],
+                                    ref["mean"], ref["rstd"], inp["dadd"])
+                e.update(kr.ln_bwd_bounds(
+                    bwd, inp["dy"], ref["s"], inp["gamma"], ref["mean"],
+                    ref["rstd"], inp["dadd"], True))
+                want = dict(ref, **{k: bwd[k] for k in (
+                    "dx", "dgamma", "dbeta", "colsum")})
+                for name, outs in _ln_mutants(inp, ref, bwd).items():
+                    out[name][(cols, rows, with_res, dy_name)] = max(
+                        kr.ratio_of(v, want[o], kr.LN_FACTOR_BF16[o] * e[o])
+                        for o, v in outs.items())
+    return out
+
+
+@pytest.mark.parametrize("mutation", LN_MUTATIONS)
+def test_ln_bounds_reject_mutation(ln_mutation_ratios, mutation):
+    ratios = ln_mutation_ratios[mutation]
+    assert ratios, mutation
+    best = max(ratios, key=ratios.get)
+    print(mutation, "worst err / allowed:", ratios[best], "at", best,
+          "; weakest case:", min(ratios.values()))
+    assert ratios[best] >= 10.0, (mutation, best, ratios[best])
+
+
+GELU_MUTATIONS = (
+    "bias_of_neighbour_vector", "erf_gelu", "derivative_without_cubic",
+    "dbias_segment_shifted", "dbias_missing_rows_from_1024")
+
+
+@pytest.fixture(scope="module")
+def gelu_mutation_ratios():
+    out = {name: {} for name in GELU_MUTATIONS}
+    for rows, cols in ((37, 24), (37, 1536), (1025, 1536)):
+        inp = kr.bias_gelu_inputs(rows, cols)
+        x, bias, dy = inp["x"], inp["bias"], inp["dy"]
+        ref = kr.bias_gelu_ref(x, bias, dy)
+        e = kr.bias_gelu_bounds(ref, x, bias, dy, True)
+        z = ref["z"]
+        mut = {}
+        shifted = kr.bias_gelu_ref(x, torch.roll(bias, 8), dy)
+        mut["bias_of_neighbour_vector"] = dict(
+            out=shifted["out"], dx=shifted["dx"], dbias=shifted["dbias"])
+        mut["erf_gelu"] = dict(out=torch.nn.functional.gelu(z))
+        dx = dy * kr.gelu_tanh_grad(z, cubic=False)
+        mut["derivative_without_cubic"] = dict(dx=dx, dbias=dx.sum(0))
+        if cols >= 1024:
+            mut["dbias_segment_shifted"] = dict(
+                dbias=torch.roll(ref["dbias"], 512))
+        if rows > 1024:
+            mut["dbias_missing_rows_from_1024"] = dict(
+                dbias=ref["dx"][:1024].sum(0))
+        for name, outs in mut.items():
+            out[name][(rows, cols)] = max(
+                kr.ratio_of(v, ref[o], kr.GELU_FACTOR_BF16[o] * e[o])
+                for o, v in outs.items())
+    return out
+
+
+@pytest.mark.parametrize("mutation", GELU_MUTATIONS)
+def test_gelu_bounds_reject_mutation(gelu_mutation_ratios, mutation):
+    ratios = gelu_mutation_ratios[mutation]
+    assert ratios, mutation
+    best = max(ratios, key=ratios.get)
+    print(mutation, "worst err / allowed:", ratios[best], "at", best)
+    assert ratios[best] >= 10.0, (mutation, best, ratios[best])
