@@ -68,13 +68,13 @@ void epl_attn_fwd(const void*, const void*, const void*, void*, float*,
                   int64_t, int64_t, float, bool, int64_t, int64_t,
                   const int64_t*,
                   const int64_t*, unsigned int*, int64_t,
-                  unsigned long long, int, float, hipStream_t);
+                  unsigned long long, int, float, const int*, hipStream_t);
 void epl_attn_bwd(const void*, const void*, const void*, const void*,
                   const void*, const float*, float*, void*, void*, void*,
                   int64_t, int64_t, float, bool, int64_t, const int64_t*,
                   const int64_t*, const int64_t*, const int64_t*, int,
                   const unsigned int*, int64_t, float, int64_t,
-                  const float*, hipStream_t);
+                  const float*, const int*, hipStream_t);
 }
 
 namespace {
@@ -371,13 +371,30 @@ static void attn_check_grid(int64_t bh, int64_t seq, bool causal) {
               bh, " exceeds the 65535 blocks of gridDim.y");
 }
 
+// seqlens: optional int32 [B] valid lengths of a right-padded batch.
+// Only its layout is checked here; the values are read (and clamped to
+// [0, seq]) by the kernels, so there is no host sync and a captured
+// graph replays with whatever lengths the tensor then holds.
+static const int* attn_seqlens(const c10::optional<at::Tensor>& seqlens,
+                               const at::Tensor& q) {
+  if (!seqlens.has_value()) return nullptr;
+  check(*seqlens, at::kInt, "seqlens");
+  TORCH_CHECK(seqlens->numel() == q.size(0), "seqlens must hold ",
+              q.size(0), " lengths (one per sample), got ",
+              seqlens->numel());
+  TORCH_CHECK(seqlens->device() == q.device(),
+              "seqlens must be on the device of q");
+  return seqlens->data_ptr<int>();
+}
+
 // drop_mask: optional int32 [bh*seq*ceil(seq/32)] keep-bit tensor the
 // kernel fills when dropout is on (drop_thresh in (0,256); the actual
 // drop probability is drop_thresh/256).
 void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
               at::Tensor lse, double scale, bool causal,
               c10::optional<at::Tensor> drop_mask, int64_t seed,
-              int64_t drop_thresh, double inv_keep) {
+              int64_t drop_thresh, double inv_keep,
+              c10::optional<at::Tensor> seqlens) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
   int64_t in_s[3], o_s[3], tmp[3];
   attn_strides(q, in_s, "q");
@@ -407,7 +424,7 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
                lse.data_ptr<float>(), bh, seq, (float)scale, causal, heads,
                head_dim, in_s, o_s, mptr, mask_w,
                (unsigned long long)seed, (int)drop_thresh,
-               (float)inv_keep, cur_stream());
+               (float)inv_keep, attn_seqlens(seqlens, q), cur_stream());
 }
 
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
@@ -415,7 +432,8 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
               at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
               bool causal, bool split_dkdv,
               c10::optional<at::Tensor> drop_mask, double inv_keep,
-              c10::optional<at::Tensor> dlse) {
+              c10::optional<at::Tensor> dlse,
+              c10::optional<at::Tensor> seqlens) {
   int64_t in_s[3], o_s[3], do_s[3], g_s[3], tmp[3];
   attn_strides(q, in_s, "q");
   attn_strides(out, o_s, "out");
@@ -449,7 +467,8 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
                delta_ws.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
                dv.data_ptr(), bh, seq, (float)scale, causal, heads, in_s,
                o_s, do_s, g_s, split_dkdv ? 1 : 0, mptr, mask_w,
-               (float)inv_keep, q.size(3), dlse_ptr, cur_stream());
+               (float)inv_keep, q.size(3), dlse_ptr,
+               attn_seqlens(seqlens, q), cur_stream());
 }
 
 // out_gather / out_tr: int16 [4 * head_dim/32, 64, 8] (fragment, lane,
@@ -588,6 +607,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_dispatch_bwd", &moe_dispatch_bwd);
   m.def("moe_combine_fwd", &moe_combine_fwd);
   m.def("moe_combine_bwd", &moe_combine_bwd);
-  m.def("attn_fwd", &attn_fwd);
-  m.def("attn_bwd", &attn_bwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("out"), py::arg("lse"), py::arg("scale"), py::arg("causal"),
+        py::arg("drop_mask"), py::arg("seed"), py::arg("drop_thresh"),
+        py::arg("inv_keep"), py::arg("seqlens") = py::none());
+  m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("delta_ws"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("scale"), py::arg("causal"), py::arg("split_dkdv"),
+        py::arg("drop_mask"), py::arg("inv_keep"), py::arg("dlse"),
+        py::arg("seqlens") = py::none());
 }

@@ -1,5 +1,6 @@
 // Hand-written CDNA4 (gfx950) flash attention, head_dim 64 and 128,
-// bf16, causal or not, optional in-kernel dropout.
+// bf16, causal or not, optional in-kernel dropout, optional per-sample
+// lengths for right-padded batches (sample_len below).
 //
 // Replaces the AOTriton SDPA kernels on the BERT/GPT hot path (BERT-Large
 // shape b128 s512 h16 d64 on MI355X: fwd ~340 us, bwd ~1190 us for the
@@ -159,6 +160,31 @@ DEVI void store_acc_bf16(short* p, const f32x16& acc, int hi) {
   }
 }
 
+// padded batches: sample b holds len = clamp(seqlens[b], 0, seq) valid
+// leading rows; the rest is right padding.  A dense call (no seqlens)
+// has len = seq.  The kernels use len wherever seq is a BOUND and keep
+// seq wherever it is a PITCH (lse/delta rows, mask words, the grid).
+// The value is block-uniform (it depends on bh alone); readfirstlane says
+// so to the compiler, which otherwise holds len per lane in VGPRs and
+// compares on the VALU (8 spilled dwords in the d64 dropout dV/dK).
+DEVI int64_t sample_len(const int* seqlens, int64_t b, int64_t seq) {
+  if (seqlens == nullptr) return seq;
+  const int64_t n = __builtin_amdgcn_readfirstlane(seqlens[b]);
+  return n < 0 ? 0 : (n > seq ? seq : n);
+}
+
+// padded rows are written as exact zeros: one lane's share of an output
+// row (the columns store_acc_bf16 covers for this hi)
+template <int D>
+DEVI void zero_row(short* p, int hi) {
+  const u32x2 z = {0u, 0u};
+#pragma unroll
+  for (int j = 0; j < D / 32; ++j)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      *reinterpret_cast<u32x2*>(p + j * 32 + 8 * g + 4 * hi) = z;
+}
+
 // ----------------------------------------------------------------------------
 // philox4x32-10 counter-based RNG for in-kernel attention dropout.
 // One call yields 16 bytes = the 16 Bernoulli draws of one lane's
@@ -300,7 +326,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
     int64_t heads, int64_t in_sb, int64_t in_sh, int64_t in_ss,
     int64_t o_sb, int64_t o_sh, int64_t o_ss,
     unsigned int* __restrict__ mask, int64_t mask_w,
-    unsigned long long seed, int drop_thresh, float inv_keep) {
+    unsigned long long seed, int drop_thresh, float inv_keep,
+    const int* __restrict__ seqlens) {
   __shared__ short ldsV[2][D][72];     // V^T: [d][kv], double-buffered
   __shared__ short ldsK[2][64][D + 8];  // K: [kv][d]
   const int lane = threadIdx.x & 63;
@@ -319,13 +346,25 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
                             : (int64_t)blockIdx.x;
   const int64_t q0_blk = qb * 128;
   const int64_t q0 = q0_blk + wave * 32;
-  const bool active = q0 < seq;
+  const int64_t len = sample_len(seqlens, bh / heads, seq);
+  const int64_t myq = q0 + lq;
+  // padded rows are written as zeros here, ahead of the loop, so that
+  // past this point seq is a pitch only and the loop holds the same
+  // scalars as before (len in the place of seq)
+  if (myq >= len && myq < seq) {
+    zero_row<D>(out + (bh / heads) * o_sb + (bh % heads) * o_sh +
+                    myq * o_ss, hi);
+    if (hi == 0) lse[bh * seq + myq] = 0.f;
+  }
+  // a block wholly inside the padding (an empty sample included) loads
+  // nothing and leaves before any barrier
+  if (q0_blk >= len) return;
+  const bool active = q0 < len;
   const short* qp = q + boff;
   const short* kp = k + boff;
   const short* vp = v + boff;
 
-  const int64_t myq = q0 + lq;
-  const int64_t qrow = myq < seq ? myq : seq - 1;
+  const int64_t qrow = myq < len ? myq : len - 1;
 
   bf16x8 qfrag[D / 16];
 #pragma unroll
@@ -337,10 +376,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
   float m = -1e30f, l = 0.f;
 
   // bulk tiles are provably full for EVERY lane of the block: below the
-  // causal diagonal (kv < q0_blk <= myq) and inside the seq bound
-  const int64_t bulk_end = causal ? q0_blk : (seq & ~(int64_t)63);
+  // causal diagonal (kv < q0_blk <= myq) and inside the length
+  const int64_t len64 = len & ~(int64_t)63;
+  const int64_t bulk_end = causal ? (q0_blk < len64 ? q0_blk : len64) : len64;
   const int64_t blk_kv_end =
-      causal ? (q0_blk + 128 < seq ? q0_blk + 128 : seq) : seq;
+      causal ? (q0_blk + 128 < len ? q0_blk + 128 : len) : len;
   const int stage_kv = threadIdx.x & 63;
   const int stage_d0 = (threadIdx.x >> 6) * 8;
 
@@ -353,7 +393,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
   bf16x8 pv[D / 32], pk[D / 32];
   auto load_tile = [&](int64_t kv0) {
     int64_t vrow = kv0 + stage_kv;
-    if (vrow >= seq) vrow = seq - 1;   // masked columns never contribute
+    if (vrow >= len) vrow = len - 1;   // masked columns never contribute
 #pragma unroll
     for (int h2 = 0; h2 < D / 32; ++h2) {
       const int sd = stage_d0 + h2 * 32;
@@ -387,7 +427,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
     if (kv0 + 64 < blk_kv_end) load_tile(kv0 + 64);
 #pragma unroll
     for (int sub = 0; sub < 64; sub += 32)
-      fwd_tile<false, DROP, D>(ldsK[buf], ldsV[buf], sub, kv0 + sub, seq,
+      fwd_tile<false, DROP, D>(ldsK[buf], ldsV[buf], sub, kv0 + sub, len,
                                myq, scale, causal, qfrag, ot, m, l, lq,
                                hi, maskrow, mask_w, seed0, seed1, bh32,
                                drop_thresh, inv_keep);
@@ -399,12 +439,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
     if (kv0 + 64 < blk_kv_end) load_tile(kv0 + 64);
     if (active) {
       const int64_t wave_kv_end = causal
-          ? (q0 + 32 < seq ? q0 + 32 : seq) : seq;
+          ? (q0 + 32 < len ? q0 + 32 : len) : len;
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t kvs = kv0 + sub;
         if (kvs >= wave_kv_end) break;
-        fwd_tile<true, DROP, D>(ldsK[buf], ldsV[buf], sub, kvs, seq, myq,
+        fwd_tile<true, DROP, D>(ldsK[buf], ldsV[buf], sub, kvs, len, myq,
                                 scale, causal, qfrag, ot, m, l, lq, hi,
                                 maskrow, mask_w, seed0, seed1, bh32,
                                 drop_thresh, inv_keep);
@@ -413,7 +453,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
     buf ^= 1;
   }
 
-  if (!active || myq >= seq) return;
+  if (!active || myq >= len) return;
   const float inv_l = 1.f / l;
   short* op = out + (bh / heads) * o_sb + (bh % heads) * o_sh + myq * o_ss;
 #pragma unroll
@@ -839,7 +879,7 @@ void attn_bwd_dv_kernel(
     int64_t do_sb, int64_t do_sh, int64_t do_ss, int64_t g_sb,
     int64_t g_sh, int64_t g_ss,
     const unsigned int* __restrict__ mask, int64_t mask_w,
-    float inv_keep) {
+    float inv_keep, const int* __restrict__ seqlens) {
   // TR: dual-use image + the chunk's 64 -lse/scale values
   constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
   __shared__ __attribute__((aligned(16))) short
@@ -857,15 +897,22 @@ void attn_bwd_dv_kernel(
   const int64_t kv0_blk =
       (causal ? (int64_t)blockIdx.y : (int64_t)blockIdx.x) * 128;
   const int64_t kv0 = kv0_blk + wave * 32;
-  const bool active = kv0 < seq;
+  const int64_t len = sample_len(seqlens, bh / heads, seq);
+  const int64_t mykv = kv0 + lkv;
+  // padded key rows are zeroed ahead of the loop and a block wholly
+  // inside the padding loads nothing (see attn_fwd_kernel)
+  if (mykv >= len && mykv < seq)
+    zero_row<D>(dv + (bh / heads) * g_sb + (bh % heads) * g_sh +
+                    mykv * g_ss, hi);
+  if (kv0_blk >= len) return;
+  const bool active = kv0 < len;
   const int64_t boff = (bh / heads) * in_sb + (bh % heads) * in_sh;
   const short* qp = q + boff;
   const short* kp = k + boff;
   const short* dop = dout + (bh / heads) * do_sb + (bh % heads) * do_sh;
   const float* lsep = lse + bh * seq;
 
-  const int64_t mykv = kv0 + lkv;
-  const int64_t kvrow = mykv < seq ? mykv : seq - 1;
+  const int64_t kvrow = mykv < len ? mykv : len - 1;
   bf16x8 kfrag[D / 16];
 #pragma unroll
   for (int c = 0; c < D / 16; ++c)
@@ -888,12 +935,12 @@ void attn_bwd_dv_kernel(
   auto prefetch = [&](int64_t q0) {
     if (TR && wave == 0) {
       const int64_t qr = q0 + lane;
-      rl = lsep[qr < seq ? qr : seq - 1] * neg_inv_scale;
+      rl = lsep[qr < len ? qr : len - 1] * neg_inv_scale;
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
-      if (qr >= seq) qr = seq - 1;
+      if (qr >= len) qr = len - 1;
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         rq[half][s] = *reinterpret_cast<const bf16x8*>(
@@ -923,12 +970,12 @@ void attn_bwd_dv_kernel(
     __syncthreads();
     if (TR && wave == 0) {
       const int64_t qr = q0 + lane;
-      ldsL[0][lane] = lsep[qr < seq ? qr : seq - 1] * neg_inv_scale;
+      ldsL[0][lane] = lsep[qr < len ? qr : len - 1] * neg_inv_scale;
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
-      if (qr >= seq) qr = seq - 1;
+      if (qr >= len) qr = len - 1;
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
@@ -953,11 +1000,11 @@ void attn_bwd_dv_kernel(
     constexpr bool M = decltype(masked)::value;
     if constexpr (TR)
       dv_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
-                             &ldsL[rb][sub], sub, q0s, seq, mykv, scale,
+                             &ldsL[rb][sub], sub, q0s, len, mykv, scale,
                              causal, kfrag, dvt, lkv, hi, maskrow, mask_w,
                              inv_keep);
     else
-      dv_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, seq, mykv, scale,
+      dv_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, len, mykv, scale,
                           causal, lsep, kfrag, dvt, lkv, hi, maskrow,
                           mask_w, inv_keep);
   };
@@ -967,8 +1014,8 @@ void attn_bwd_dv_kernel(
   // unified 64-row chunk loop; the phase test (masked causal diagonal /
   // branch-free bulk / masked seq tail) is block-uniform per chunk
   const int64_t diag_end =
-      causal ? (kv0_blk + 128 < seq ? kv0_blk + 128 : seq) : 0;
-  const int64_t bulk_end = seq & ~(int64_t)63;
+      causal ? (kv0_blk + 128 < len ? kv0_blk + 128 : len) : 0;
+  const int64_t bulk_end = len & ~(int64_t)63;
   if (!DBUF) {
     // two-barrier direct staging, phase-split loops (the measured r2
     // baseline — kept verbatim so the fallback stays spill-free)
@@ -990,13 +1037,13 @@ void attn_bwd_dv_kernel(
       for (int sub = 0; sub < 64; sub += 32)
         tile(PLAIN_T, 0, sub, q0 + sub);
     }
-    for (; q0 < seq; q0 += 64) {
+    for (; q0 < len; q0 += 64) {
       stage_q64(q0);
       if (!active) continue;
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t q0s = q0 + sub;
-        if (q0s >= seq) break;
+        if (q0s >= len) break;
         tile(MASKED_T, 0, sub, q0s);
       }
     }
@@ -1004,10 +1051,10 @@ void attn_bwd_dv_kernel(
     const int64_t q_begin = causal ? kv0_blk : 0;
     int buf = 0;
     prefetch(q_begin);
-    for (int64_t q0 = q_begin; q0 < seq; q0 += 64) {
+    for (int64_t q0 = q_begin; q0 < len; q0 += 64) {
       commit(buf);
       __syncthreads();
-      if (q0 + 64 < seq) prefetch(q0 + 64);
+      if (q0 + 64 < len) prefetch(q0 + 64);
       const int rb = buf;
       buf ^= 1;
       const bool plain = q0 >= diag_end && q0 + 63 < bulk_end;
@@ -1019,14 +1066,14 @@ void attn_bwd_dv_kernel(
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32) {
           const int64_t q0s = q0 + sub;
-          if (q0s >= seq) break;
+          if (q0s >= len) break;
           if (causal && q0s + 31 < kv0) continue;
           tile(MASKED_T, rb, sub, q0s);
         }
       }
     }
   }
-  if (!active || mykv >= seq) return;
+  if (!active || mykv >= len) return;
   short* dvp = dv + (bh / heads) * g_sb + (bh % heads) * g_sh +
                mykv * g_ss;
 #pragma unroll
@@ -1051,7 +1098,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     int64_t do_sb, int64_t do_sh, int64_t do_ss, int64_t g_sb,
     int64_t g_sh, int64_t g_ss,
     const unsigned int* __restrict__ mask, int64_t mask_w,
-    float inv_keep) {
+    float inv_keep, const int* __restrict__ seqlens) {
   constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
   __shared__ __attribute__((aligned(16))) short
       ldsQ[DBUF ? 2 : 1][64][PITCH];
@@ -1067,7 +1114,15 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
   const int64_t kv0_blk =
       (causal ? (int64_t)blockIdx.y : (int64_t)blockIdx.x) * 128;
   const int64_t kv0 = kv0_blk + wave * 32;
-  const bool active = kv0 < seq;
+  const int64_t len = sample_len(seqlens, bh / heads, seq);
+  const int64_t mykv = kv0 + lkv;
+  // padded key rows are zeroed ahead of the loop and a block wholly
+  // inside the padding loads nothing (see attn_fwd_kernel)
+  if (mykv >= len && mykv < seq)
+    zero_row<D>(dk + (bh / heads) * g_sb + (bh % heads) * g_sh +
+                    mykv * g_ss, hi);
+  if (kv0_blk >= len) return;
+  const bool active = kv0 < len;
   const int64_t boff = (bh / heads) * in_sb + (bh % heads) * in_sh;
   const short* qp = q + boff;
   const short* kp = k + boff;
@@ -1076,8 +1131,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
   const float* lsep = lse + bh * seq;
   const float* dltp = delta + bh * seq;
 
-  const int64_t mykv = kv0 + lkv;
-  const int64_t kvrow = mykv < seq ? mykv : seq - 1;
+  const int64_t kvrow = mykv < len ? mykv : len - 1;
   bf16x8 kfrag[D / 16], vfrag[D / 16];
 #pragma unroll
   for (int c = 0; c < D / 16; ++c) {
@@ -1098,13 +1152,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
   auto prefetch = [&](int64_t q0) {
     if (TR && wave < 2) {
       const int64_t qr = q0 + lane;
-      rl = (wave == 0 ? lsep : dltp)[qr < seq ? qr : seq - 1] *
+      rl = (wave == 0 ? lsep : dltp)[qr < len ? qr : len - 1] *
            (wave == 0 ? neg_inv_scale : -1.f);
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
-      if (qr >= seq) qr = seq - 1;
+      if (qr >= len) qr = len - 1;
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         rq[half][s] = *reinterpret_cast<const bf16x8*>(
@@ -1135,13 +1189,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     if (TR && wave < 2) {
       const int64_t qr = q0 + lane;
       ldsL[0][wave][lane] =
-          (wave == 0 ? lsep : dltp)[qr < seq ? qr : seq - 1] *
+          (wave == 0 ? lsep : dltp)[qr < len ? qr : len - 1] *
           (wave == 0 ? neg_inv_scale : -1.f);
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t qr = q0 + stage_row + half * 32;
-      if (qr >= seq) qr = seq - 1;
+      if (qr >= len) qr = len - 1;
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
@@ -1167,18 +1221,18 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     if constexpr (TR)
       dk_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
                              &ldsL[rb][0][sub], &ldsL[rb][1][sub], sub,
-                             q0s, seq, mykv, scale, causal, kfrag, vfrag,
+                             q0s, len, mykv, scale, causal, kfrag, vfrag,
                              dkt, lkv, hi, maskrow, mask_w, inv_keep);
     else
-      dk_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, seq, mykv, scale,
+      dk_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, len, mykv, scale,
                           causal, lsep, dltp, kfrag, vfrag, dkt, lkv, hi,
                           maskrow, mask_w, inv_keep);
   };
   constexpr std::true_type MASKED_T{};
   constexpr std::false_type PLAIN_T{};
   const int64_t diag_end =
-      causal ? (kv0_blk + 128 < seq ? kv0_blk + 128 : seq) : 0;
-  const int64_t bulk_end = seq & ~(int64_t)63;
+      causal ? (kv0_blk + 128 < len ? kv0_blk + 128 : len) : 0;
+  const int64_t bulk_end = len & ~(int64_t)63;
   if (!DBUF) {
     int64_t q0 = causal ? kv0_blk : 0;
     for (; q0 < diag_end; q0 += 64) {
@@ -1198,13 +1252,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
       for (int sub = 0; sub < 64; sub += 32)
         tile(PLAIN_T, 0, sub, q0 + sub);
     }
-    for (; q0 < seq; q0 += 64) {
+    for (; q0 < len; q0 += 64) {
       stage_q64(q0);
       if (!active) continue;
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32) {
         const int64_t q0s = q0 + sub;
-        if (q0s >= seq) break;
+        if (q0s >= len) break;
         tile(MASKED_T, 0, sub, q0s);
       }
     }
@@ -1212,10 +1266,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     const int64_t q_begin = causal ? kv0_blk : 0;
     int buf = 0;
     prefetch(q_begin);
-    for (int64_t q0 = q_begin; q0 < seq; q0 += 64) {
+    for (int64_t q0 = q_begin; q0 < len; q0 += 64) {
       commit(buf);
       __syncthreads();
-      if (q0 + 64 < seq) prefetch(q0 + 64);
+      if (q0 + 64 < len) prefetch(q0 + 64);
       const int rb = buf;
       buf ^= 1;
       const bool plain = q0 >= diag_end && q0 + 63 < bulk_end;
@@ -1227,14 +1281,14 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32) {
           const int64_t q0s = q0 + sub;
-          if (q0s >= seq) break;
+          if (q0s >= len) break;
           if (causal && q0s + 31 < kv0) continue;
           tile(MASKED_T, rb, sub, q0s);
         }
       }
     }
   }
-  if (!active || mykv >= seq) return;
+  if (!active || mykv >= len) return;
   short* dkp = dk + (bh / heads) * g_sb + (bh % heads) * g_sh +
                mykv * g_ss;
 #pragma unroll
@@ -1385,7 +1439,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     int64_t in_ss, int64_t do_sb, int64_t do_sh, int64_t do_ss,
     int64_t g_sb, int64_t g_sh, int64_t g_ss, int64_t o_sb, int64_t o_sh,
     int64_t o_ss, const unsigned int* __restrict__ mask, int64_t mask_w,
-    float inv_keep, const float* __restrict__ dlse) {
+    float inv_keep, const float* __restrict__ dlse,
+    const int* __restrict__ seqlens) {
   constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
   __shared__ __attribute__((aligned(16))) short
       ldsK[DBUF ? 2 : 1][64][PITCH];
@@ -1401,15 +1456,23 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
                             : (int64_t)blockIdx.x;
   const int64_t q0_blk = qb * 128;
   const int64_t q0 = q0_blk + wave * 32;
-  const bool active = q0 < seq;
+  const int64_t len = sample_len(seqlens, bh / heads, seq);
+  const int64_t myq = q0 + lq;
+  // padded query rows are zeroed ahead of the loop and a block wholly
+  // inside the padding loads nothing (see attn_fwd_kernel); the delta of
+  // padded rows stays unwritten — the dK kernel never reads it
+  if (myq >= len && myq < seq)
+    zero_row<D>(dq + (bh / heads) * g_sb + (bh % heads) * g_sh +
+                    myq * g_ss, hi);
+  if (q0_blk >= len) return;
+  const bool active = q0 < len;
   const int64_t boff = (bh / heads) * in_sb + (bh % heads) * in_sh;
   const short* qp = q + boff;
   const short* kp = k + boff;
   const short* vp = v + boff;
   const short* dop = dout + (bh / heads) * do_sb + (bh % heads) * do_sh;
 
-  const int64_t myq = q0 + lq;
-  const int64_t qrow = myq < seq ? myq : seq - 1;
+  const int64_t qrow = myq < len ? myq : len - 1;
   const float mylse = lse[bh * seq + qrow];
 
   const short* op_ = out + (bh / heads) * o_sb + (bh % heads) * o_sh;
@@ -1436,7 +1499,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
   float mydelta = dsum + __shfl_xor(dsum, 32, 64);
   if (dlse != nullptr) mydelta -= dlse[bh * seq + qrow];
   // publish delta for the dK kernel that follows on the same stream
-  if (myq < seq && hi == 0)
+  if (myq < len && hi == 0)
     const_cast<float*>(delta)[bh * seq + myq] = mydelta;
 
   f32x16 dqt[D / 32] = {};
@@ -1445,16 +1508,17 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
   const int stage_seg = (threadIdx.x & 7) * 8;
   // bulk chunks (64 kv rows) are full for every lane; q0_blk is a
   // multiple of 128 so the causal bulk region is 64-aligned
-  const int64_t bulk_end = causal ? q0_blk : (seq & ~(int64_t)63);
+  const int64_t len64 = len & ~(int64_t)63;
+  const int64_t bulk_end = causal ? (q0_blk < len64 ? q0_blk : len64) : len64;
   const int64_t blk_kv_end =
-      causal ? (q0_blk + 128 < seq ? q0_blk + 128 : seq) : seq;
+      causal ? (q0_blk + 128 < len ? q0_blk + 128 : len) : len;
 
   auto stage_kv64 = [&](int64_t kv0) {
     __syncthreads();
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t kr = kv0 + stage_row + half * 32;
-      if (kr >= seq) kr = seq - 1;   // dS there is 0
+      if (kr >= len) kr = len - 1;   // dS there is 0
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
@@ -1480,7 +1544,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       int64_t kr = kv0 + stage_row + half * 32;
-      if (kr >= seq) kr = seq - 1;
+      if (kr >= len) kr = len - 1;
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         rk[half][s] = *reinterpret_cast<const bf16x8*>(
@@ -1513,11 +1577,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     constexpr bool M = decltype(masked)::value;
     if constexpr (TR)
       dq_tile_tr<M, DROP, D>(&ldsK[rb][0][0], &ldsVr[rb][0][0], sub, kvs,
-                             seq, myq, scale, causal, mylse, mydelta,
+                             len, myq, scale, causal, mylse, mydelta,
                              qfrag, dofrag, dqt, lq, hi, maskrow, mask_w,
                              inv_keep);
     else
-      dq_tile<M, DROP, D>(ldsK[rb], ldsVr[rb], sub, kvs, seq, myq, scale,
+      dq_tile<M, DROP, D>(ldsK[rb], ldsVr[rb], sub, kvs, len, myq, scale,
                           causal, mylse, mydelta, qfrag, dofrag, dqt, lq,
                           hi, maskrow, mask_w, inv_keep);
   };
@@ -1534,7 +1598,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     for (; kv0 < blk_kv_end; kv0 += 64) {
       stage_kv64(kv0);
       const int64_t wave_kv_end = causal
-          ? (q0 + 32 < seq ? q0 + 32 : seq) : seq;
+          ? (q0 + 32 < len ? q0 + 32 : len) : len;
       if (!active) continue;
 #pragma unroll
       for (int sub = 0; sub < 64; sub += 32) {
@@ -1558,7 +1622,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
           tile(PLAIN_T, rb, sub, kv0 + sub);
       } else if (active) {
         const int64_t wave_kv_end = causal
-            ? (q0 + 32 < seq ? q0 + 32 : seq) : seq;
+            ? (q0 + 32 < len ? q0 + 32 : len) : len;
 #pragma unroll
         for (int sub = 0; sub < 64; sub += 32) {
           const int64_t kvs = kv0 + sub;
@@ -1569,7 +1633,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     }
   }
 
-  if (!active || myq >= seq) return;
+  if (!active || myq >= len) return;
   short* dqp = dq + (bh / heads) * g_sb + (bh % heads) * g_sh + myq * g_ss;
 #pragma unroll
   for (int dj = 0; dj < D / 32; ++dj) {
@@ -1593,7 +1657,7 @@ void epl_attn_fwd(const void* q, const void* k, const void* v, void* out,
                   const int64_t* in_strides,
                   const int64_t* o_strides, unsigned int* drop_mask,
                   int64_t mask_w, unsigned long long seed, int drop_thresh,
-                  float inv_keep, hipStream_t stream) {
+                  float inv_keep, const int* seqlens, hipStream_t stream) {
   // causal: (x=bh, y=qblocks) — x-fastest dispatch launches every
   // batch-head of the longest q-block first (kernels read the mapping
   // from the causal flag)
@@ -1605,7 +1669,8 @@ void epl_attn_fwd(const void* q, const void* k, const void* v, void* out,
       reinterpret_cast<const short*>(v), reinterpret_cast<short*>(out),  \
       lse, seq, scale, causal ? 1 : 0, heads, in_strides[0],             \
       in_strides[1], in_strides[2], o_strides[0], o_strides[1],          \
-      o_strides[2], drop_mask, mask_w, seed, drop_thresh, inv_keep
+      o_strides[2], drop_mask, mask_w, seed, drop_thresh, inv_keep,      \
+      seqlens
   if (head_dim == 128) {
     if (drop_mask != nullptr)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_kernel<true, 128>),
@@ -1632,15 +1697,17 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
                   const int64_t* g_strides, int split_dkdv,
                   const unsigned int* drop_mask, int64_t mask_w,
                   float inv_keep, int64_t head_dim, const float* dlse,
-                  hipStream_t stream) {
+                  const int* seqlens, hipStream_t stream) {
   const int64_t rows = batch_heads * seq;
   const unsigned nqb = (unsigned)((seq + 127) / 128);
   dim3 grid = causal ? dim3((unsigned)batch_heads, nqb)
                      : dim3(nqb, (unsigned)batch_heads);
   // head_dim 128 and causal always run the split kernels (the combined
   // dkdv kernel is d=64-only and keeps the legacy x-major grid)
+  // per-sample lengths run the split kernels too (the combined kernel
+  // and its prep pass know no padding)
   if (split_dkdv || drop_mask != nullptr || head_dim == 128 || causal ||
-      dlse != nullptr) {
+      dlse != nullptr || seqlens != nullptr) {
     // order: dV (needs no delta) -> dQ (computes + publishes delta from
     // the dO/O rows it already loads) -> dK (consumes delta).  The prep
     // pass disappears.  Dropout always runs the split kernels (the
@@ -1651,7 +1718,7 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
       reinterpret_cast<short*>(dv), seq, scale, causal ? 1 : 0, heads,   \
       in_strides[0], in_strides[1], in_strides[2], do_strides[0],        \
       do_strides[1], do_strides[2], g_strides[0], g_strides[1],          \
-      g_strides[2], drop_mask, mask_w, inv_keep
+      g_strides[2], drop_mask, mask_w, inv_keep, seqlens
 #define DQ_ARGS                                                          \
   reinterpret_cast<const short*>(q), reinterpret_cast<const short*>(k),  \
       reinterpret_cast<const short*>(v),                                 \
@@ -1660,7 +1727,8 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
       seq, scale, causal ? 1 : 0, heads, in_strides[0], in_strides[1],   \
       in_strides[2], do_strides[0], do_strides[1], do_strides[2],        \
       g_strides[0], g_strides[1], g_strides[2], o_strides[0],            \
-      o_strides[1], o_strides[2], drop_mask, mask_w, inv_keep, dlse
+      o_strides[1], o_strides[2], drop_mask, mask_w, inv_keep, dlse,     \
+      seqlens
 #define DK_ARGS                                                          \
   reinterpret_cast<const short*>(q), reinterpret_cast<const short*>(k),  \
       reinterpret_cast<const short*>(v),                                 \
@@ -1668,7 +1736,7 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
       reinterpret_cast<short*>(dk), seq, scale, causal ? 1 : 0, heads,   \
       in_strides[0], in_strides[1], in_strides[2], do_strides[0],        \
       do_strides[1], do_strides[2], g_strides[0], g_strides[1],          \
-      g_strides[2], drop_mask, mask_w, inv_keep
+      g_strides[2], drop_mask, mask_w, inv_keep, seqlens
     // d64 staging mode (EPL_ATTN_BWD_DBUF): 0 = two-barrier direct
     // staging; 1 = dV double-buffered single-barrier pipeline
     // (spill-free); 2 = dK pipelined too (spills 12-40 VGPRs at 3
@@ -1783,7 +1851,8 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
                      in_strides[2], do_strides[0], do_strides[1],
                      do_strides[2], g_strides[0], g_strides[1],
                      g_strides[2], o_strides[0], o_strides[1],
-                     o_strides[2], drop_mask, mask_w, inv_keep, dlse);
+                     o_strides[2], drop_mask, mask_w, inv_keep, dlse,
+                     (const int*)nullptr);
 }
 
 }  // extern "C"

@@ -24,11 +24,20 @@ BERT_CONFIGS = {
 
 
 class BertCore(nn.Module):
-    """Single-module BERT (used when num_stages == 1)."""
+    """Single-module BERT (used when num_stages == 1).
+
+    pad_token_id: when set, every forward takes the samples' lengths from
+    the ids (``(ids != pad_token_id).sum(1)``, on the device, no host
+    sync) and the attention kernels treat the rest of each row as RIGHT
+    padding: valid positions neither see the padding nor pay for it.
+    ``forward(ids, seqlens=...)`` takes explicit int32 [B] lengths
+    instead.  Logits at padded positions are meaningless; give them the
+    target -100."""
 
     def __init__(self, layers, hidden, heads, ffn, vocab_size, max_pos,
-                 dropout=0.0):
+                 dropout=0.0, pad_token_id=None):
         super().__init__()
+        self.pad_token_id = pad_token_id
         self.embeddings = Embeddings(vocab_size, hidden, max_pos)
         self.blocks = nn.ModuleList(
             Block(hidden, heads, ffn, causal=False, pre_ln=False,
@@ -36,10 +45,12 @@ class BertCore(nn.Module):
             for _ in range(layers))
         self.head = LMHead(hidden, vocab_size)
 
-    def forward(self, ids):
+    def forward(self, ids, seqlens=None):
+        if seqlens is None and self.pad_token_id is not None:
+            seqlens = (ids != self.pad_token_id).sum(1).int()
         x = self.embeddings(ids)
         for b in self.blocks:
-            x = b(x)
+            x = b(x) if seqlens is None else b(x, seqlens=seqlens)
         return self.head(x)
 
 
@@ -68,16 +79,23 @@ class _Stage(nn.Module):
 
 
 def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
-               num_stages=1, dropout=0.0):
+               num_stages=1, dropout=0.0, pad_token_id=None):
     """Build BERT under epl annotations.  vocab defaults to 30528
-    (30522 rounded up to /8 for the fused CE kernel's vectorized path)."""
+    (30522 rounded up to /8 for the fused CE kernel's vectorized path).
+    pad_token_id: train on right-padded batches (see BertCore); single
+    stage only."""
     cfg = BERT_CONFIGS[config] if isinstance(config, str) else dict(config)
     L, H, A, F = cfg["layers"], cfg["hidden"], cfg["heads"], cfg["ffn"]
     if num_stages <= 1:
         with epl.replicate(device_count=1, name="stage_0"):
             model = BertCore(L, H, A, F, vocab_size, max_pos,
-                             dropout=dropout)
+                             dropout=dropout, pad_token_id=pad_token_id)
         return init_weights(model)
+    if pad_token_id is not None:
+        raise ValueError(
+            "pad_token_id needs num_stages == 1: a pipeline stage boundary "
+            "carries a single tensor (the hidden states), so the sequence "
+            "lengths cannot reach the attention of the later stages")
     per = (L + num_stages - 1) // num_stages
     stages = []
     layer_idx = 0
@@ -97,7 +115,12 @@ def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
 
 
 def synthetic_mlm_batch(batch, seq_len, vocab_size=30528, device="cpu",
-                        mask_frac=0.15, seed=None):
+                        mask_frac=0.15, seed=None, lengths=None,
+                        pad_token_id=0):
+    """Random MLM batch.  lengths: optional per-sample valid lengths (a
+    sequence of ``batch`` ints): positions past a sample's length hold
+    pad_token_id and the target -100.  Without lengths the batch is what
+    it always was for a seed."""
     g = torch.Generator(device="cpu")
     if seed is not None:
         g.manual_seed(seed)
@@ -106,4 +129,9 @@ def synthetic_mlm_batch(batch, seq_len, vocab_size=30528, device="cpu",
     mask = torch.rand(batch, seq_len, generator=g) < mask_frac
     targets[~mask] = -100  # only predict masked positions
     ids[mask] = 103        # [MASK]
+    if lengths is not None:
+        lens = torch.as_tensor(lengths, dtype=torch.long).reshape(batch, 1)
+        pad = torch.arange(seq_len)[None, :] >= lens
+        ids[pad] = pad_token_id
+        targets[pad] = -100
     return ids.to(device), targets.to(device)

@@ -80,26 +80,32 @@ class SelfAttention(nn.Module):
         self.proj = _Linear(hidden, hidden)
         self.dropout = dropout
 
-    def forward(self, x, bias_grad_to_ln=False):
+    def forward(self, x, bias_grad_to_ln=False, seqlens=None):
         """bias_grad_to_ln: the caller feeds the result straight into a
-        FusedLayerNorm and takes (out, lin_bias) — see linear_for_ln."""
-        o = self._attend(x)
+        FusedLayerNorm and takes (out, lin_bias) — see linear_for_ln.
+        seqlens: int32 [B] valid lengths of a right-padded batch (see
+        ops/attention.py); the padded rows of the attention output are
+        zero, so the projection returns its bias there."""
+        o = self._attend(x, seqlens)
         if bias_grad_to_ln:
             return linear_for_ln(self.proj, o)
         return self.proj(o)
 
-    def _attend(self, x):
+    def _attend(self, x, seqlens=None):
         from easyparallellibrary_amd.ops.attention import (
             flash_attention, qkv_flash_attention, qkv_native_ok)
         b, s, h = x.shape
         qkv = self.qkv(x).reshape(b, s, 3, self.num_heads, self.head_dim)
         native_here = _NATIVE_ATTN in ("1", "auto")
         p = self.dropout if self.training else 0.0
+        # dense calls keep the call they always made
+        lens = {} if seqlens is None else {"seqlens": seqlens}
         if native_here and qkv_native_ok(qkv):
             # fully fused: kernels read the qkv views and write d_qkv
             # slices directly — no unbind/stack copies at all; dropout
             # runs in-kernel (philox keep-mask, p quantized to 1/256)
-            o = qkv_flash_attention(qkv, causal=self.causal, dropout_p=p)
+            o = qkv_flash_attention(qkv, causal=self.causal, dropout_p=p,
+                                    **lens)
             return o.transpose(1, 2).reshape(b, s, h)
         if _QKV_SPLIT:
             q, k, v = _QKVSplit.apply(qkv)
@@ -109,7 +115,7 @@ class SelfAttention(nn.Module):
             k = k.transpose(1, 2)
             v = v.transpose(1, 2)
         o = flash_attention(q, k, v, causal=self.causal,
-                            allow_native=native_here, dropout_p=p)
+                            allow_native=native_here, dropout_p=p, **lens)
         return o.transpose(1, 2).reshape(b, s, h)
 
 
@@ -143,23 +149,28 @@ class Block(nn.Module):
         self.mlp = MLP(hidden, ffn_hidden)
 
     @staticmethod
-    def _into_ln(mod, cls, x):
+    def _into_ln(mod, cls, x, **kwargs):
         """mod(x) for a FusedLayerNorm consumer -> (out, lin_bias); a
-        wrapped or replaced submodule runs as the plain call it expects."""
+        wrapped or replaced submodule runs as the plain call it expects
+        (plus the keyword arguments that are set, e.g. seqlens)."""
+        kwargs = {k: v for k, v in kwargs.items() if v is not None}
         if type(mod) is cls:
-            return mod(x, bias_grad_to_ln=True)
-        return mod(x), None
+            return mod(x, bias_grad_to_ln=True, **kwargs)
+        return mod(x, **kwargs), None
 
-    def forward(self, x):
+    def forward(self, x, seqlens=None):
+        """seqlens: int32 [B] valid lengths of a right-padded batch; only
+        the attention looks at it (every other op is per token)."""
         if self.pre_ln:
             # residual add fused into ln2; the summed stream s is the
             # residual carried forward
-            a, pb = self._into_ln(self.attn, SelfAttention, self.ln1(x))
+            a, pb = self._into_ln(self.attn, SelfAttention, self.ln1(x),
+                                  seqlens=seqlens)
             y, s = self.ln2.forward_with_sum(a, x, lin_bias=pb)
             return s + self.mlp(y)
         # post-LN: both residual adds fuse into the LN kernels, and the
         # LN backward returns the bias gradient of the Linear before it
-        a, pb = self._into_ln(self.attn, SelfAttention, x)
+        a, pb = self._into_ln(self.attn, SelfAttention, x, seqlens=seqlens)
         x = self.ln1(a, residual=x, lin_bias=pb)
         m, fb = self._into_ln(self.mlp, MLP, x)
         x = self.ln2(m, residual=x, lin_bias=fb)

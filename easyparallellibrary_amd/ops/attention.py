@@ -8,6 +8,14 @@ kernels (csrc/kernels/attention.hip) keep the whole online softmax in
 registers — swapped QK^T so each lane owns one query row, O accumulated
 transposed so the rescale is lane-local, P fragments rebuilt with
 v_permlane32_swap.  CPU / unsupported shapes fall back to torch SDPA.
+
+Padded batches: ``seqlens`` (int32 [B], on the device of q) gives every
+sample's number of valid leading tokens; the rest is right padding.
+Query i < len attends keys j < len (and j <= i when causal); rows past
+the length of out and of every gradient are exact zeros, and nothing at
+a valid position depends on what the padding holds.  The kernels read
+and clamp the lengths themselves (no host sync), skip the padded tiles
+and exit whole blocks past the length.
 """
 
 import torch
@@ -49,10 +57,37 @@ def _drop_params(dropout_p):
     return thresh, inv_keep, seed
 
 
+def seqlens_from_mask(mask):
+    """int32 [B] lengths from a [B, S] attention mask (non-zero = token).
+    RIGHT padding only: the result is ``mask.sum(1)``, which describes
+    the batch only when every sample's tokens come first."""
+    return (mask != 0).sum(1).int()
+
+
+def _check_seqlens(seqlens, q):
+    if seqlens is None:
+        return None
+    if seqlens.dtype != torch.int32 or seqlens.dim() != 1 \
+            or seqlens.shape[0] != q.shape[0]:
+        raise ValueError("seqlens must be int32 [B={}], got {} {}".format(
+            q.shape[0], seqlens.dtype, tuple(seqlens.shape)))
+    if seqlens.device != q.device:
+        raise ValueError("seqlens must be on the device of q")
+    return seqlens.contiguous()
+
+
 def _mask_tensor(b, h, seq, device):
     mask_w = (seq + 31) // 32
     return torch.empty(b * h * seq * mask_w, dtype=torch.int32,
                        device=device)
+
+
+def _saved_optionals(ctx, rest):
+    """(mask, seqlens) from the tail of the saved tensors"""
+    rest = list(rest)
+    mask = rest.pop(0) if ctx.has_mask else None
+    seqlens = rest.pop(0) if ctx.has_seqlens else None
+    return mask, seqlens
 
 
 class _FlashAttention(torch.autograd.Function):
@@ -63,7 +98,7 @@ class _FlashAttention(torch.autograd.Function):
     republished to the backward kernels; p quantized to 1/256)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, dropout_p=0.0):
+    def forward(ctx, q, k, v, causal, scale, dropout_p=0.0, seqlens=None):
         if not (_kernel_ok(q) and _kernel_ok(k) and _kernel_ok(v)
                 and q.stride() == k.stride() == v.stride()):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
@@ -75,11 +110,13 @@ class _FlashAttention(torch.autograd.Function):
         thresh, inv_keep, seed = _drop_params(dropout_p)
         mask = _mask_tensor(b, h, seq, q.device) if thresh else None
         native_ext().attn_fwd(q, k, v, out, lse, scale, causal, mask,
-                              seed, thresh, inv_keep)
-        if mask is None:
-            ctx.save_for_backward(q, k, v, out, lse)
-        else:
-            ctx.save_for_backward(q, k, v, out, lse, mask)
+                              seed, thresh, inv_keep, seqlens)
+        # optional tensors ride save_for_backward (checkpoint unpack
+        # hooks see them); the flags say which ones are there
+        ctx.has_mask = mask is not None
+        ctx.has_seqlens = seqlens is not None
+        ctx.save_for_backward(q, k, v, out, lse, *[
+            t for t in (mask, seqlens) if t is not None])
         ctx.causal = causal
         ctx.scale = scale
         ctx.inv_keep = inv_keep
@@ -90,7 +127,7 @@ class _FlashAttention(torch.autograd.Function):
         import os
         saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
         q, k, v, out, lse = saved[:5]
-        mask = saved[5] if len(saved) > 5 else None
+        mask, seqlens = _saved_optionals(ctx, saved[5:])
         # the bwd kernels re-stage q/k/v/dout tiles every 32-row iteration;
         # strided rows (6 KB apart in the qkv views) measured +405us/call
         # vs 4 contiguization copies at ~43us each — copy for backward only
@@ -117,8 +154,8 @@ class _FlashAttention(torch.autograd.Function):
         split = os.environ.get("EPL_ATTN_BWD_SPLIT", "1") == "1"
         native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv,
                               ctx.scale, ctx.causal, split, mask,
-                              ctx.inv_keep, None)
-        return dq, dk, dv, None, None, None
+                              ctx.inv_keep, None, seqlens)
+        return dq, dk, dv, None, None, None, None
 
 
 class _QKVFlashAttention(torch.autograd.Function):
@@ -130,7 +167,7 @@ class _QKVFlashAttention(torch.autograd.Function):
     3x-oversized ``empty_strided`` transients."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, scale, dropout_p=0.0):
+    def forward(ctx, qkv, causal, scale, dropout_p=0.0, seqlens=None):
         b, s, three, h, d = qkv.shape
         q = qkv[:, :, 0].transpose(1, 2)
         k = qkv[:, :, 1].transpose(1, 2)
@@ -141,11 +178,11 @@ class _QKVFlashAttention(torch.autograd.Function):
         thresh, inv_keep, seed = _drop_params(dropout_p)
         mask = _mask_tensor(b, h, s, qkv.device) if thresh else None
         native_ext().attn_fwd(q, k, v, out, lse, scale, causal, mask,
-                              seed, thresh, inv_keep)
-        if mask is None:
-            ctx.save_for_backward(qkv, out, lse)
-        else:
-            ctx.save_for_backward(qkv, out, lse, mask)
+                              seed, thresh, inv_keep, seqlens)
+        ctx.has_mask = mask is not None
+        ctx.has_seqlens = seqlens is not None
+        ctx.save_for_backward(qkv, out, lse, *[
+            t for t in (mask, seqlens) if t is not None])
         ctx.causal = causal
         ctx.scale = scale
         ctx.inv_keep = inv_keep
@@ -155,7 +192,7 @@ class _QKVFlashAttention(torch.autograd.Function):
     def backward(ctx, dout):
         saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
         qkv, out, lse = saved[:3]
-        mask = saved[3] if len(saved) > 3 else None
+        mask, seqlens = _saved_optionals(ctx, saved[3:])
         q = qkv[:, :, 0].transpose(1, 2)
         k = qkv[:, :, 1].transpose(1, 2)
         v = qkv[:, :, 2].transpose(1, 2)
@@ -168,8 +205,8 @@ class _QKVFlashAttention(torch.autograd.Function):
         delta = torch.empty_like(lse)
         native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv,
                               ctx.scale, ctx.causal, True, mask,
-                              ctx.inv_keep, None)
-        return dqkv, None, None, None
+                              ctx.inv_keep, None, seqlens)
+        return dqkv, None, None, None, None
 
 
 class _FlashAttentionLse(torch.autograd.Function):
@@ -237,16 +274,41 @@ def flash_attention_with_lse(q, k, v, causal=False, scale=None):
     return out, lse
 
 
-def qkv_flash_attention(qkv, causal=False, scale=None, dropout_p=0.0):
+def _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens):
+    """The padded-batch semantics of the kernels in torch ops (CPU and
+    non-native shapes): a key mask, then zeros on the padded query rows.
+    An empty sample is masked as if it held one key, so its softmax rows
+    are finite and the ``where`` below hands no NaN to the backward; its
+    rows are all padding and come out zero like any other.  The padded
+    rows of q, k, v are replaced by zeros first: a masked NaN would
+    otherwise come through the matmuls as 0 * NaN."""
+    seq = q.shape[-2]
+    lens = seqlens.clamp(0, seq)
+    pos = torch.arange(seq, device=q.device)
+    keys = pos[None, :] < lens.clamp(min=1)[:, None]          # [B, S]
+    attn_mask = keys[:, None, None, :]
+    if causal:
+        attn_mask = attn_mask & (pos[None, :] <= pos[:, None])
+    rows = (pos[None, :] < lens[:, None])[:, None, :, None]    # [B,1,S,1]
+    q, k, v = (torch.where(rows, t, torch.zeros_like(t)) for t in (q, k, v))
+    out = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask,
+                                         scale=scale, dropout_p=dropout_p)
+    return torch.where(rows, out, torch.zeros_like(out))
+
+
+def qkv_flash_attention(qkv, causal=False, scale=None, dropout_p=0.0,
+                        seqlens=None):
     """qkv: [B, S, 3, H, D] (the fused projection output).  Returns
     attention output as a [B, H, S, D] view whose memory order is
     [B, S, H, D] (the caller's transpose+reshape is free).  Requires the
     native kernels (bf16, D=64); callers fall back to the split-views +
     SDPA path otherwise.  dropout_p is applied in-kernel (philox mask,
-    p quantized to 1/256) — pass it only in training mode."""
+    p quantized to 1/256) — pass it only in training mode.  seqlens:
+    int32 [B] valid lengths of a right-padded batch (module docstring)."""
     if scale is None:
         scale = qkv.shape[-1] ** -0.5
-    return _QKVFlashAttention.apply(qkv, causal, scale, dropout_p)
+    seqlens = _check_seqlens(seqlens, qkv)
+    return _QKVFlashAttention.apply(qkv, causal, scale, dropout_p, seqlens)
 
 
 def qkv_native_ok(qkv):
@@ -256,15 +318,21 @@ def qkv_native_ok(qkv):
 
 
 def flash_attention(q, k, v, causal=False, scale=None, allow_native=True,
-                    dropout_p=0.0):
+                    dropout_p=0.0, seqlens=None):
     """q,k,v: [B, H, S, D].  Native kernel when bf16/D=64 on GPU; torch
     SDPA otherwise.  dropout_p runs in-kernel on the native path
-    (training-mode callers only)."""
+    (training-mode callers only).  seqlens: int32 [B] valid lengths of a
+    right-padded batch (module docstring); the fallback keeps the same
+    semantics."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    seqlens = _check_seqlens(seqlens, q)
     if allow_native and use_native(q):
         if q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
-            return _FlashAttention.apply(q, k, v, causal, scale, dropout_p)
+            return _FlashAttention.apply(q, k, v, causal, scale, dropout_p,
+                                         seqlens)
         _warn_fallback("dtype={} head_dim={}".format(q.dtype, q.shape[-1]))
+    if seqlens is not None:
+        return _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens)
     return F.scaled_dot_product_attention(q, k, v, is_causal=causal,
                                           scale=scale, dropout_p=dropout_p)
