@@ -3,22 +3,30 @@
 // lengths for right-padded batches (sample_len below).
 //
 // Replaces the AOTriton SDPA kernels on the BERT/GPT hot path (BERT-Large
-// shape b128 s512 h16 d64 on MI355X: fwd ~340 us, bwd ~1190 us for the
-// three kernels; profiles/attn_bwd_tiles_ab.txt).
+// shape b128 s512 h16 d64 on MI355X: bwd ~1190 us for the three kernels,
+// profiles/attn_bwd_tiles_ab.txt; fwd profiles/attn_fwd_lean_ab.txt).
 //
-// Forward structure (cdna_hip_programming.md section B recipe, adapted to
-// one 32-row q-block per wave, 32-key kv tiles, head_dim 64):
+// Forward structure (one 32-row q-block per wave, 64-key kv tiles taken
+// as two 32-key sub-tiles):
 //  * swapped QK^T: S^T = K @ Q^T via v_mfma_f32_32x32x16_bf16, so each
 //    lane owns ONE q-row's scores (16 kv values per lane, the partner
-//    lane l^32 holds the other 16) -> online softmax is 15 reg-max ops +
-//    one shfl_xor(32) exchange, no LDS.
+//    lane l^32 holds the other 16) -> the row max is 8 v_max3 + one
+//    v_permlane32_swap exchange, no LDS.
+//  * the running max is kept on the RAW accumulator values and
+//    P = exp2(fma(S, scale*log2e, -m*scale*log2e)): one fma per v_exp_f32.
 //  * O accumulated TRANSPOSED: O^T = V^T @ P^T, so the online rescale by
-//    alpha = exp(m_old - m_new) is a lane-local scalar multiply.
+//    alpha is a lane-local scalar multiply; it is DEFERRED: a wave-uniform
+//    branch takes it only when a row max grew by more than 2^8, else the
+//    stale max stays (P <= 2^8).  Row sums stay per-lane partials until
+//    the epilogue.
 //  * P^T fragments assembled in-register: pack f32 pairs to bf16 dwords
-//    and exchange halves with v_permlane32_swap (T12).
-//  * Q/K fragments are contiguous 16-byte row segments loaded straight
-//    from global (L2-resident tiles); V^T fragments gather columns (L2).
-// Saves per-row LSE (m + log l) for the backward.
+//    and exchange halves with v_permlane32_swap.
+//  * K and V tiles are staged alike, 8 lanes per 128-byte row piece
+//    (whole cache lines per load instruction); K is read back by rows
+//    (ds_read_b128), V sits in the dual-use row image of
+//    attn_lds_image.h and its V^T operands are ds_read_b64_tr_b16 reads.
+//  * O is parked in the freed K buffers and stored as whole rows.
+// Saves per-row LSE (m*scale + log l) for the backward.
 //
 // Backward: three kernels launched dV -> dQ -> dK (kv-parallel for dV
 // and dK, q-parallel for dQ), each lane owning its output row — no
@@ -106,7 +114,8 @@ DEVI bf16x8 assemble_pfrag(const float* p) {
 }
 
 // dual-use LDS image (row reads + transposed reads) of the backward's
-// new tile bodies: layout and fragment readers in attn_lds_image.h
+// new tile bodies and of the forward's V tile: layout and fragment
+// readers in attn_lds_image.h
 using attn_img::img_off;
 using attn_img::img_pitch;
 using attn_img::tr_frag;
@@ -219,11 +228,13 @@ DEVI void philox4x32(unsigned int c0, unsigned int c1, unsigned int c2,
 }
 
 // ============================================================================
-// forward (v3): KVBLK = 64; K (row copies) and V^T (transposed, 144-
-// byte row pad -> conflict-free ds_read_b128 fragments) staged in LDS
-// once per block per tile.  Measured: explicit double-buffering and
+// forward (v4): KVBLK = 64; K (padded row copies, conflict-free
+// ds_read_b128 fragments) and V (row image, transposed reads) staged in
+// LDS once per block per tile.  Measured: explicit double-buffering and
 // register prefetch both REGRESS (hipcc schedules the simple form best
-// at 3 waves/SIMD) - keep this structure.
+// at 3-4 waves/SIMD) - keep this structure.  One softmax step per 64-key
+// tile (both S sub-tiles first) measured the same as two 32-key steps and
+// spills the d64 dropout kernel (profiles/attn_fwd_lean_ab.txt).
 //
 // v3: the kv loop is SPLIT into a branch-free bulk phase (tiles that are
 // provably full: no seq-bound or causal masking, no per-wave break — the
@@ -235,16 +246,43 @@ DEVI void philox4x32(unsigned int c0, unsigned int c1, unsigned int c2,
 // tiles, not just diagonal ones.
 // ============================================================================
 
-// one 32-key sub-tile of the fwd online-softmax loop; MASKED adds the
-// seq-bound + causal-diagonal masking (bulk tiles skip all of it);
-// DROP generates + applies + publishes the dropout keep-mask (the
-// normalizer l accumulates UNDROPPED exp values, so lse and the
-// backward's P are dropout-free; O accumulates P*keep/(1-p)*V)
+// the value of the partner lane (l ^ 32) by v_permlane32_swap: swapping a
+// register with itself leaves the low half's value in one result and the
+// high half's in the other, in every lane.  EXEC all ones.
+DEVI void both_halves(unsigned int x, unsigned int& lo, unsigned int& hi_) {
+  const i32x2 r = __builtin_amdgcn_permlane32_swap((int)x, (int)x, false,
+                                                   false);
+  lo = (unsigned int)r[0];
+  hi_ = (unsigned int)r[1];
+}
+
+// deferred rescale: the running max m moves only when some row of the
+// wave has grown past it by more than this many powers of two, so P
+// stays <= 2^kRescaleThr (docs/kernels.md)
+constexpr float kRescaleThr = 8.f;
+
+// one 32-key sub-tile of the fwd online-softmax loop: the S products, one
+// max exchange, one rescale decision, the exponentials, the PV products.
+//  * m and the maxima are RAW accumulator values (scale > 0 commutes
+//    with max); c2 = scale * log2(e) is folded into the one fma that
+//    feeds v_exp_f32, and lse is put back into score units in the
+//    epilogue.
+//  * l is this lane's PARTIAL row sum: the partner lane (l ^ 32) applies
+//    the same alpha throughout, so the halves add exactly in the epilogue.
+//  * the rescale of ot and l is a wave-uniform branch on a vote, taken
+//    before the first exponential of the step; on the other path m keeps
+//    its stale value, so l, ot and lse always belong to the same m.
+// MASKED adds the seq-bound + causal-diagonal masking (bulk tiles skip
+// all of it); DROP generates + applies + publishes the dropout keep-mask
+// per 32-key sub-tile (the normalizer l accumulates UNDROPPED exp values,
+// so lse and the backward's P are dropout-free; O accumulates
+// P*keep/(1-p)*V).  V^T operands come straight from the row image by
+// ds_read_b64_tr_b16 (tr_frag: EXEC all ones, so every caller sits in
+// wave-uniform control flow).
 template <bool MASKED, bool DROP, int D>
-DEVI void fwd_tile(const short (&ldsK)[64][D + 8],
-                   const short (&ldsV)[D][72],
+DEVI void fwd_tile(const short (&ldsK)[64][D + 8], const short* imgV,
                    int sub, int64_t kvs, int64_t seq, int64_t myq,
-                   float scale, int causal, const bf16x8 (&qfrag)[D / 16],
+                   float c2, int causal, const bf16x8 (&qfrag)[D / 16],
                    f32x16 (&ot)[D / 32], float& m, float& l, int lq,
                    int hi, unsigned int* maskrow, int64_t mask_w,
                    unsigned int seed0, unsigned int seed1,
@@ -261,7 +299,7 @@ DEVI void fwd_tile(const short (&ldsK)[64][D + 8],
   float tile_max = -1e30f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    float sv = st[r] * scale;
+    float sv = st[r];
     if (MASKED) {
       const int64_t kvg = kvs + crow(r, hi);
       if (kvg >= seq || (causal && kvg > myq)) sv = -1e30f;
@@ -269,18 +307,31 @@ DEVI void fwd_tile(const short (&ldsK)[64][D + 8],
     s[r] = sv;
     tile_max = fmaxf(tile_max, sv);
   }
-  tile_max = fmaxf(tile_max, __shfl_xor(tile_max, 32, 64));
-  const float m_new = fmaxf(m, tile_max);
-  const float alpha = __expf(m - m_new);
+  {
+    unsigned int a, b;
+    both_halves(__builtin_bit_cast(unsigned int, tile_max), a, b);
+    tile_max = fmaxf(__builtin_bit_cast(float, a),
+                     __builtin_bit_cast(float, b));
+  }
+  if (__builtin_amdgcn_ballot_w64((tile_max - m) * c2 > kRescaleThr) != 0) {
+    const float m_new = fmaxf(m, tile_max);
+    const float alpha = __builtin_amdgcn_exp2f((m - m_new) * c2);
+    m = m_new;
+    l *= alpha;
+#pragma unroll
+    for (int j = 0; j < D / 32; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        ot[j][r] *= alpha;
+  }
+  const float nmc = -m * c2;
   float rowsum = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    s[r] = __expf(s[r] - m_new);
+    s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, nmc));
     rowsum += s[r];
   }
-  rowsum += __shfl_xor(rowsum, 32, 64);
-  l = l * alpha + rowsum;
-  m = m_new;
+  l += rowsum;
   if (DROP) {
     unsigned int rnd[4];
     philox4x32((unsigned int)myq,
@@ -294,15 +345,11 @@ DEVI void fwd_tile(const short (&ldsK)[64][D + 8],
       s[r] = keep ? s[r] * inv_keep : 0.f;
       mybits |= (unsigned int)keep << crow(r, hi);
     }
-    const unsigned int word = mybits | __shfl_xor(mybits, 32, 64);
+    unsigned int wlo, whi;
+    both_halves(mybits, wlo, whi);
     if (hi == 0 && myq < seq)
-      maskrow[myq * mask_w + (kvs >> 5)] = word;
+      maskrow[myq * mask_w + (kvs >> 5)] = wlo | whi;
   }
-#pragma unroll
-  for (int j = 0; j < D / 32; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      ot[j][r] *= alpha;
   bf16x8 pf0 = assemble_pfrag<true>(&s[0]);
   bf16x8 pf1 = assemble_pfrag<true>(&s[8]);
 #pragma unroll
@@ -310,8 +357,7 @@ DEVI void fwd_tile(const short (&ldsK)[64][D + 8],
     bf16x8 pf = kc == 0 ? pf0 : pf1;
 #pragma unroll
     for (int j = 0; j < D / 32; ++j) {
-      bf16x8 vt = *reinterpret_cast<const bf16x8*>(
-          &ldsV[j * 32 + lq][sub + kc * 16 + hi * 8]);
+      bf16x8 vt = tr_frag<D>(imgV, sub + 16 * kc, j, hi * 32 + lq);
       ot[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt, pf, ot[j], 0, 0,
                                                       0);
     }
@@ -328,8 +374,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
     unsigned int* __restrict__ mask, int64_t mask_w,
     unsigned long long seed, int drop_thresh, float inv_keep,
     const int* __restrict__ seqlens) {
-  __shared__ short ldsV[2][D][72];     // V^T: [d][kv], double-buffered
-  __shared__ short ldsK[2][64][D + 8];  // K: [kv][d]
+  // V: [kv][d] row image (attn_lds_image.h), read transposed for PV
+  __shared__ __attribute__((aligned(16))) short
+      ldsV[2][64 * img_pitch<D>()];
+  // K: [kv][d] padded rows; after the loop, the block's 128 O rows
+  __shared__ __attribute__((aligned(16))) short ldsK[2][64][D + 8];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
@@ -373,7 +422,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
         qp + qrow * in_ss + hi * 8 + 16 * c);
 
   f32x16 ot[D / 32] = {};
+  // m: running RAW row maximum; l: this lane's partial row sum (fwd_tile)
   float m = -1e30f, l = 0.f;
+  const float c2 = scale * 1.44269504088896341f;
 
   // bulk tiles are provably full for EVERY lane of the block: below the
   // causal diagonal (kv < q0_blk <= myq) and inside the length
@@ -381,8 +432,6 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
   const int64_t bulk_end = causal ? (q0_blk < len64 ? q0_blk : len64) : len64;
   const int64_t blk_kv_end =
       causal ? (q0_blk + 128 < len ? q0_blk + 128 : len) : len;
-  const int stage_kv = threadIdx.x & 63;
-  const int stage_d0 = (threadIdx.x >> 6) * 8;
 
   // Single-barrier double-buffered staging: the NEXT tile's global
   // loads issue right after the barrier and their latency hides under
@@ -390,26 +439,39 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
   // (start of the next iteration) is where the vmcnt wait lands.  One
   // __syncthreads per 64-kv tile instead of two (PMC r2: 38% of
   // wave-cycles were parked at barriers).
-  bf16x8 pv[D / 32], pk[D / 32];
+  // Eight consecutive lanes fetch one 128-byte piece of a row, so a wave
+  // instruction covers 8 whole cache lines (a lane per row touched 64)
+  // and lands as one conflict-free ds_write_b128 per 8 lanes; K and V
+  // are staged alike.
+  const int stage_row = threadIdx.x >> 3;        // 0..31, +32 per half
+  const int stage_seg = (threadIdx.x & 7) * 8;   // +64 per 128-byte piece
+  bf16x8 pv[2][D / 64], pk[2][D / 64];
   auto load_tile = [&](int64_t kv0) {
-    int64_t vrow = kv0 + stage_kv;
-    if (vrow >= len) vrow = len - 1;   // masked columns never contribute
 #pragma unroll
-    for (int h2 = 0; h2 < D / 32; ++h2) {
-      const int sd = stage_d0 + h2 * 32;
-      pv[h2] = *reinterpret_cast<const bf16x8*>(vp + vrow * in_ss + sd);
-      pk[h2] = *reinterpret_cast<const bf16x8*>(kp + vrow * in_ss + sd);
+    for (int half = 0; half < 2; ++half) {
+      int64_t vrow = kv0 + stage_row + half * 32;
+      if (vrow >= len) vrow = len - 1;   // masked columns never contribute
+#pragma unroll
+      for (int s = 0; s < D / 64; ++s) {
+        const int col = stage_seg + s * 64;
+        pv[half][s] =
+            *reinterpret_cast<const bf16x8*>(vp + vrow * in_ss + col);
+        pk[half][s] =
+            *reinterpret_cast<const bf16x8*>(kp + vrow * in_ss + col);
+      }
     }
   };
   auto write_tile = [&](int b) {
 #pragma unroll
-    for (int h2 = 0; h2 < D / 32; ++h2) {
-      const int sd = stage_d0 + h2 * 32;
+    for (int half = 0; half < 2; ++half)
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        ldsV[b][sd + j][stage_kv] = pv[h2][j];
-      *reinterpret_cast<bf16x8*>(&ldsK[b][stage_kv][sd]) = pk[h2];
-    }
+      for (int s = 0; s < D / 64; ++s) {
+        const int row = stage_row + half * 32;
+        const int col = stage_seg + s * 64;
+        *reinterpret_cast<bf16x8*>(
+            &ldsV[b][img_off<D>(row, col >> 3)]) = pv[half][s];
+        *reinterpret_cast<bf16x8*>(&ldsK[b][row][col]) = pk[half][s];
+      }
   };
 
   unsigned int* maskrow =
@@ -428,8 +490,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
 #pragma unroll
     for (int sub = 0; sub < 64; sub += 32)
       fwd_tile<false, DROP, D>(ldsK[buf], ldsV[buf], sub, kv0 + sub, len,
-                               myq, scale, causal, qfrag, ot, m, l, lq,
-                               hi, maskrow, mask_w, seed0, seed1, bh32,
+                               myq, c2, causal, qfrag, ot, m, l, lq, hi,
+                               maskrow, mask_w, seed0, seed1, bh32,
                                drop_thresh, inv_keep);
     buf ^= 1;
   }
@@ -445,7 +507,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
         const int64_t kvs = kv0 + sub;
         if (kvs >= wave_kv_end) break;
         fwd_tile<true, DROP, D>(ldsK[buf], ldsV[buf], sub, kvs, len, myq,
-                                scale, causal, qfrag, ot, m, l, lq, hi,
+                                c2, causal, qfrag, ot, m, l, lq, hi,
                                 maskrow, mask_w, seed0, seed1, bh32,
                                 drop_thresh, inv_keep);
       }
@@ -453,13 +515,39 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
     buf ^= 1;
   }
 
-  if (!active || myq >= len) return;
+  // the two lanes of a row applied the same alpha throughout, so their
+  // partial sums add exactly.  No wave has diverged or left since the
+  // loop: EXEC is all ones for the swap.
+  {
+    unsigned int a, b;
+    both_halves(__builtin_bit_cast(unsigned int, l), a, b);
+    l = __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+  }
   const float inv_l = 1.f / l;
-  short* op = out + (bh / heads) * o_sb + (bh % heads) * o_sh + myq * o_ss;
+  short* ob = out + (bh / heads) * o_sb + (bh % heads) * o_sh;
+  // O leaves through the K buffers, now free: each lane parks its row
+  // (8-byte pieces), then eight (d128: sixteen) lanes store one whole row
+  // as 16-byte pieces.  A lane per row wrote 8 bytes to each of 32 lines
+  // per instruction.  Waves past len park garbage and store nothing;
+  // every wave of the block reaches both barriers.
+  short* ldsO = &ldsK[0][0][0] + wave * 32 * (D + 8);
+  __syncthreads();              // every wave is done with the last K tile
 #pragma unroll
   for (int j = 0; j < D / 32; ++j)
-    store_acc_bf16(op + j * 32, ot[j] * inv_l, hi);
-  if (hi == 0) lse[bh * seq + myq] = m + __logf(l);
+    store_acc_bf16(ldsO + lq * (D + 8) + j * 32, ot[j] * inv_l, hi);
+  __syncthreads();
+  constexpr int LPR = D / 8;    // lanes per row
+#pragma unroll
+  for (int r0 = 0; r0 < 32; r0 += 64 / LPR) {
+    const int r = r0 + lane / LPR;
+    const int col = (lane % LPR) * 8;
+    const bf16x8 piece =
+        *reinterpret_cast<const bf16x8*>(ldsO + r * (D + 8) + col);
+    if (q0 + r < len)
+      *reinterpret_cast<bf16x8*>(ob + (q0 + r) * o_ss + col) = piece;
+  }
+  // m is a raw maximum; lse is in score units
+  if (hi == 0 && myq < len) lse[bh * seq + myq] = m * scale + __logf(l);
 }
 
 // ============================================================================

@@ -1,7 +1,9 @@
-// Dual-use LDS image of a [64][D] bf16 tile for the attention backward
-// (new tile bodies) and the tr_read_probe kernel that checks it.
+// Dual-use LDS image of a [64][D] bf16 tile for the attention kernels
+// (the backward's new tile bodies; the forward's V tile, of which only
+// the transposed read is used) and the tr_read_probe kernel that checks
+// it.
 //
-// One copy of a Q / dO / K tile serves both kinds of MFMA operand read:
+// One copy of a Q / dO / K / V tile serves both kinds of MFMA operand read:
 //  * row fragments, ds_read_b128 at [row][8*ch .. 8*ch+7];
 //  * transposed fragments, two ds_read_b64_tr_b16 per bf16x8 operand.
 // Every store and load goes through img_off, so the layout lives here
