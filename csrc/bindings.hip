@@ -64,6 +64,14 @@ void epl_moe_combine_bwd(void*, float*, const void*, const void*,
                          const float*, const int64_t*, const int64_t*,
                          const int64_t*, int64_t, int64_t, int64_t,
                          hipStream_t);
+int64_t epl_moe_router_waves(int64_t, int64_t);
+void epl_moe_router_fwd(const void*, int64_t*, float*, float*, int64_t*,
+                        float*, float*, float*, int*, int64_t, int64_t,
+                        int64_t, bool, bool, hipStream_t);
+void epl_moe_router_bwd(void*, const void*, const float*, const int64_t*,
+                        const float*, const int64_t*, const float*,
+                        const float*, int64_t, int64_t, int64_t, bool, bool,
+                        hipStream_t);
 void epl_attn_fwd(const void*, const void*, const void*, void*, float*,
                   int64_t, int64_t, float, bool, int64_t, int64_t,
                   const int64_t*,
@@ -558,6 +566,85 @@ void moe_combine_bwd(at::Tensor dh, at::Tensor dfw, at::Tensor dout,
                       cur_stream());
 }
 
+static bool aligned16(const at::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// N tokens, E experts of a [N, E] logits tensor, checked against k
+static void router_extents(const at::Tensor& logits, int64_t k, int64_t* n,
+                           int64_t* e) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() &&
+              logits.dim() == 2,
+              "logits must be a contiguous 2-D device tensor");
+  *n = logits.size(0);
+  *e = logits.size(1);
+  TORCH_CHECK(k == 1 || k == 2, "moe router: k must be 1 or 2, got ", k);
+  TORCH_CHECK(*e >= 2 && *e <= 256,
+              "moe router: 2 <= num_experts <= 256, got ", *e);
+  TORCH_CHECK(*n >= 1 && *n < (int64_t(1) << 30),
+              "moe router: 1 <= tokens < 2^30, got ", *n);
+}
+
+void moe_router_fwd(at::Tensor logits, int64_t k, at::Tensor topi,
+                    at::Tensor topw, at::Tensor lse, at::Tensor counts,
+                    at::Tensor psum, at::Tensor losses) {
+  const bool bf16 = is_bf16(logits);
+  int64_t n, e;
+  router_extents(logits, k, &n, &e);
+  check_idx(topi, "topi");
+  check(topw, at::kFloat, "topw");
+  check(lse, at::kFloat, "lse");
+  check_idx(counts, "counts");
+  check(psum, at::kFloat, "psum");
+  check(losses, at::kFloat, "losses");
+  TORCH_CHECK(topi.numel() == n * k && topw.numel() == n * k,
+              "topi / topw must hold tokens * k elements");
+  TORCH_CHECK(lse.numel() == n, "lse must hold one element per token");
+  TORCH_CHECK(counts.numel() == e && psum.numel() == e,
+              "counts / psum must hold one element per expert");
+  TORCH_CHECK(losses.numel() == 2, "losses must hold 2 elements");
+  const int64_t waves = epl_moe_router_waves(n, e);
+  at::Tensor p_part = at::empty({waves * e + waves},
+                                logits.options().dtype(at::kFloat));
+  at::Tensor c_part = at::empty({waves * e},
+                                logits.options().dtype(at::kInt));
+  epl_moe_router_fwd(logits.data_ptr(), topi.data_ptr<int64_t>(),
+                     topw.data_ptr<float>(), lse.data_ptr<float>(),
+                     counts.data_ptr<int64_t>(), psum.data_ptr<float>(),
+                     losses.data_ptr<float>(), p_part.data_ptr<float>(),
+                     c_part.data_ptr<int>(), n, e, k, bf16,
+                     aligned16(logits), cur_stream());
+}
+
+void moe_router_bwd(at::Tensor dlogits, at::Tensor logits, at::Tensor lse,
+                    at::Tensor topi, at::Tensor dw, at::Tensor counts,
+                    at::Tensor g_bal, at::Tensor g_z, int64_t k) {
+  const bool bf16 = is_bf16(logits);
+  int64_t n, e;
+  router_extents(logits, k, &n, &e);
+  check(dlogits, logits.scalar_type(), "dlogits");
+  TORCH_CHECK(dlogits.numel() == n * e, "dlogits must match logits");
+  check(lse, at::kFloat, "lse");
+  check_idx(topi, "topi");
+  check(dw, at::kFloat, "dw");
+  check_idx(counts, "counts");
+  check(g_bal, at::kFloat, "g_bal");
+  check(g_z, at::kFloat, "g_z");
+  TORCH_CHECK(lse.numel() == n, "lse must hold one element per token");
+  TORCH_CHECK(topi.numel() == n * k && dw.numel() == n * k,
+              "topi / dw must hold tokens * k elements");
+  TORCH_CHECK(counts.numel() == e,
+              "counts must hold one element per expert");
+  TORCH_CHECK(g_bal.numel() == 1 && g_z.numel() == 1,
+              "g_bal / g_z must hold one element");
+  epl_moe_router_bwd(dlogits.data_ptr(), logits.data_ptr(),
+                     lse.data_ptr<float>(), topi.data_ptr<int64_t>(),
+                     dw.data_ptr<float>(), counts.data_ptr<int64_t>(),
+                     g_bal.data_ptr<float>(), g_z.data_ptr<float>(), n, e, k,
+                     bf16, aligned16(logits) && aligned16(dlogits),
+                     cur_stream());
+}
+
 void colsum(at::Tensor dy, at::Tensor db, at::Tensor partial) {
   const bool bf16 = is_bf16(dy);
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 2,
@@ -607,6 +694,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_dispatch_bwd", &moe_dispatch_bwd);
   m.def("moe_combine_fwd", &moe_combine_fwd);
   m.def("moe_combine_bwd", &moe_combine_bwd);
+  m.def("moe_router_fwd", &moe_router_fwd);
+  m.def("moe_router_bwd", &moe_router_bwd);
+  m.def("moe_router_waves", [](int64_t n, int64_t e) {
+    return epl_moe_router_waves(n, e);
+  });
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("out"), py::arg("lse"), py::arg("scale"), py::arg("causal"),
         py::arg("drop_mask"), py::arg("seed"), py::arg("drop_thresh"),

@@ -15,7 +15,8 @@ from easyparallellibrary_amd.ops.moe import ExpertParallelMLP
 
 class MoEBlock(nn.Module):
     def __init__(self, hidden, heads, ffn, num_experts, split_degree=1,
-                 top_k=2, make_moe=True):
+                 top_k=2, make_moe=True, aux_loss_coef=0.0,
+                 z_loss_coef=0.0):
         super().__init__()
         self.ln1 = FusedLayerNorm(hidden)
         self.attn = SelfAttention(hidden, heads, causal=True)
@@ -23,7 +24,9 @@ class MoEBlock(nn.Module):
         if make_moe:
             with epl.split(device_count=split_degree, name="experts"):
                 self.moe = ExpertParallelMLP(hidden, ffn, num_experts,
-                                             top_k=top_k)
+                                             top_k=top_k,
+                                             aux_loss_coef=aux_loss_coef,
+                                             z_loss_coef=z_loss_coef)
         else:
             self.moe = None  # attached later (pipeline builder)
 
@@ -36,12 +39,13 @@ class MoEBlock(nn.Module):
 class MoETransformer(nn.Module):
     def __init__(self, layers=4, hidden=512, heads=8, ffn=2048,
                  num_experts=8, vocab_size=32000, max_pos=1024, top_k=2,
-                 split_degree=1):
+                 split_degree=1, aux_loss_coef=0.0, z_loss_coef=0.0):
         super().__init__()
         self.embeddings = Embeddings(vocab_size, hidden, max_pos,
                                      use_ln=False)
         self.blocks = nn.ModuleList(
-            MoEBlock(hidden, heads, ffn, num_experts, split_degree, top_k)
+            MoEBlock(hidden, heads, ffn, num_experts, split_degree, top_k,
+                     aux_loss_coef=aux_loss_coef, z_loss_coef=z_loss_coef)
             for _ in range(layers))
         self.head = LMHead(hidden, vocab_size)
 
@@ -86,7 +90,8 @@ class MoEPipelineModel(nn.Module):
 
 def build_moe_pipeline(stages=2, ep=1, layers=4, hidden=512, heads=8,
                        ffn=2048, num_experts=8, vocab_size=32000,
-                       max_pos=1024, top_k=2):
+                       max_pos=1024, top_k=2, aux_loss_coef=0.0,
+                       z_loss_coef=0.0):
     """PP x (DP+EP) hybrid: stage ``s`` is a ``replicate(ep)`` scope over
     ``ep`` ranks (positions act as data-parallel streams); its expert
     weights live in a per-stage ``split(ep)`` scope that colocates with
@@ -112,7 +117,9 @@ def build_moe_pipeline(stages=2, ep=1, layers=4, hidden=512, heads=8,
         with epl.split(device_count=ep, name="experts_{}".format(s)):
             for b in blocks:
                 b.moe = ExpertParallelMLP(hidden, ffn, num_experts,
-                                          top_k=top_k)
+                                          top_k=top_k,
+                                          aux_loss_coef=aux_loss_coef,
+                                          z_loss_coef=z_loss_coef)
     return init_weights(MoEPipelineModel(stage_mods))
 
 

@@ -436,6 +436,10 @@ class Engine:
         optimizer) so callers can drive their own accumulation loop; the
         next ``accumulate=False`` call reduces everything accumulated and
         steps once, dividing by the number of accumulated calls."""
+        # MoE aux losses inject their gradient inside backward: it has to
+        # carry the loss scale of this step (constant within a step)
+        from easyparallellibrary_amd.ops.moe import set_aux_loss_scale
+        set_aux_loss_scale(self.amp.loss_scale)
         if accumulate:
             if self.pipeline is not None:
                 raise ValueError(

@@ -21,6 +21,7 @@ ext = CUDAExtension(
         "csrc/comm/rccl_comm.hip",
         "csrc/kernels/kernels.hip",
         "csrc/kernels/moe.hip",
+        "csrc/kernels/moe_router.hip",
         "csrc/kernels/mfma_probe.hip",
         "csrc/kernels/attention.hip",
     ],
