@@ -83,6 +83,18 @@ void epl_attn_bwd(const void*, const void*, const void*, const void*,
                   const int64_t*, const int64_t*, const int64_t*, int,
                   const unsigned int*, int64_t, float, int64_t,
                   const float*, const int*, hipStream_t);
+void epl_rms_norm_fwd(void*, const void*, const void*, void*, const void*,
+                      float*, int64_t, int64_t, float, hipStream_t);
+int64_t epl_rms_norm_bwd_parts(int64_t, int64_t);
+void epl_rms_norm_bwd(void*, float*, const void*, const void*, const void*,
+                      const float*, const void*, float*, int64_t, int64_t,
+                      hipStream_t);
+void epl_rope(void*, const float*, const float*, int64_t, int64_t, int64_t,
+              int64_t, int64_t, int64_t, int64_t, int64_t, bool,
+              hipStream_t);
+void epl_swiglu_fwd(void*, const void*, int64_t, int64_t, hipStream_t);
+void epl_swiglu_bwd(void*, const void*, const void*, int64_t, int64_t,
+                    hipStream_t);
 }
 
 namespace {
@@ -665,6 +677,164 @@ void sqnorm(at::Tensor t, at::Tensor out) {
              cur_stream());
 }
 
+// ---- LLaMA ops (csrc/kernels/llama_ops.hip) --------------------------------
+// Everything a launch relies on is checked here from the tensors' metadata
+// alone: no value is read on the host, so the ops stay graph-capturable.
+
+// contiguous bf16 on `dev` with a 16-byte-aligned base
+static void check_llama_bf16(const at::Tensor& t, const at::Device& dev,
+                             const char* name) {
+  check(t, at::kBFloat16, name);
+  TORCH_CHECK(t.device() == dev, name, " is on another device");
+  TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
+}
+
+static void check_llama_f32(const at::Tensor& t, const at::Device& dev,
+                            int64_t numel, const char* name) {
+  check(t, at::kFloat, name);
+  TORCH_CHECK(t.device() == dev, name, " is on another device");
+  TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
+  TORCH_CHECK(t.numel() == numel, name, " must hold ", numel, " elements");
+}
+
+// rows, cols of a native RMSNorm operand x: bf16, 8 <= cols <= 8192, cols % 8
+static void rms_extents(const at::Tensor& x, int64_t* rows, int64_t* cols) {
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "rms_norm: empty input");
+  *cols = x.size(-1);
+  *rows = x.numel() / *cols;
+  TORCH_CHECK(*cols % 8 == 0 && *cols >= 8 && *cols <= 8192,
+              "rms_norm: native widths are multiples of 8 up to 8192, got ",
+              *cols);
+}
+
+// out = s rstd gamma with s = x (+ res), rstd = rsqrt(mean(s^2) + eps);
+// with res the summed stream is written to s_out.  rstd: fp32 [rows].
+void rms_norm_fwd(at::Tensor out, at::Tensor x, c10::optional<at::Tensor> res,
+                  c10::optional<at::Tensor> s_out, at::Tensor gamma,
+                  at::Tensor rstd, double eps) {
+  int64_t rows, cols;
+  const at::Device dev = x.device();
+  check_llama_bf16(x, dev, "x");
+  rms_extents(x, &rows, &cols);
+  check_llama_bf16(out, dev, "out");
+  check_llama_bf16(gamma, dev, "gamma");
+  TORCH_CHECK(out.numel() == x.numel(), "out must match x");
+  TORCH_CHECK(gamma.numel() == cols, "gamma must hold cols elements");
+  check_llama_f32(rstd, dev, rows, "rstd");
+  TORCH_CHECK(res.has_value() == s_out.has_value(),
+              "rms_norm_fwd: res and s come together");
+  const void* res_p = nullptr;
+  void* s_p = nullptr;
+  if (res.has_value()) {
+    check_llama_bf16(*res, dev, "res");
+    check_llama_bf16(*s_out, dev, "s");
+    TORCH_CHECK(res->numel() == x.numel() && s_out->numel() == x.numel(),
+                "res and s must match x");
+    res_p = res->data_ptr();
+    s_p = s_out->data_ptr();
+  }
+  epl_rms_norm_fwd(out.data_ptr(), x.data_ptr(), res_p, s_p,
+                   gamma.data_ptr(), rstd.data_ptr<float>(), rows, cols,
+                   (float)eps, cur_stream());
+}
+
+// dx = rstd (dy gamma - xhat mean(dy gamma xhat)) (+ dadd), xhat = s rstd;
+// dgamma (fp32 [cols], overwritten) = sum_rows dy xhat
+void rms_norm_bwd(at::Tensor dx, at::Tensor dgamma, at::Tensor dy,
+                  at::Tensor s, at::Tensor gamma, at::Tensor rstd,
+                  c10::optional<at::Tensor> dadd) {
+  int64_t rows, cols;
+  const at::Device dev = s.device();
+  check_llama_bf16(s, dev, "s");
+  rms_extents(s, &rows, &cols);
+  check_llama_bf16(dx, dev, "dx");
+  check_llama_bf16(dy, dev, "dy");
+  check_llama_bf16(gamma, dev, "gamma");
+  TORCH_CHECK(dx.numel() == s.numel() && dy.numel() == s.numel(),
+              "dx and dy must match s");
+  TORCH_CHECK(gamma.numel() == cols, "gamma must hold cols elements");
+  check_llama_f32(dgamma, dev, cols, "dgamma");
+  check_llama_f32(rstd, dev, rows, "rstd");
+  const void* dadd_p = nullptr;
+  if (dadd.has_value()) {
+    check_llama_bf16(*dadd, dev, "dadd");
+    TORCH_CHECK(dadd->numel() == s.numel(), "dadd must match s");
+    dadd_p = dadd->data_ptr();
+  }
+  const int64_t nparts = epl_rms_norm_bwd_parts(rows, cols);
+  at::Tensor ws = at::empty({nparts, cols}, dgamma.options());
+  epl_rms_norm_bwd(dx.data_ptr(), dgamma.data_ptr<float>(), dy.data_ptr(),
+                   s.data_ptr(), gamma.data_ptr(), rstd.data_ptr<float>(),
+                   dadd_p, ws.data_ptr<float>(), rows, cols, cur_stream());
+}
+
+// In-place rotary embedding of a [B, S, N, D] view (see rope_kernel):
+// rows pos0 .. pos0 + S - 1 of the fp32 [L, D / 2] tables; inverse applies
+// the transposed rotation.
+void rope_(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, int64_t pos0,
+           bool inverse) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
+              "rope_: x must be a bf16 device tensor");
+  TORCH_CHECK(x.dim() == 4, "rope_: x must be a [B, S, N, D] view");
+  const int64_t b = x.size(0), s = x.size(1), n = x.size(2), d = x.size(3);
+  TORCH_CHECK(d == 64 || d == 128, "rope_: head_dim must be 64 or 128, got ",
+              d);
+  TORCH_CHECK(x.stride(3) == 1, "rope_: last dim must be contiguous");
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(x.size(i) == 1 || (x.stride(i) % 8 == 0 && x.stride(i) >= d),
+                "rope_: stride ", i, " must be a multiple of 8 elements "
+                "and at least one head, got ", x.stride(i));
+  TORCH_CHECK(aligned16(x), "rope_: x must be 16-byte aligned");
+  TORCH_CHECK(b * s * n * (d / 16) < (int64_t(1) << 31),
+              "rope_: too many elements for one launch");
+  const at::Device dev = x.device();
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(1) == d / 2,
+              "rope_: tables must be [L, D / 2]");
+  check_llama_f32(cos_t, dev, cos_t.size(0) * (d / 2), "cos");
+  check_llama_f32(sin_t, dev, cos_t.numel(), "sin");
+  TORCH_CHECK(pos0 >= 0 && pos0 + s <= cos_t.size(0), "rope_: positions ",
+              pos0, " .. ", pos0 + s, " exceed the table length ",
+              cos_t.size(0));
+  epl_rope(x.data_ptr(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+           x.stride(0), x.stride(1), x.stride(2), b, s, n, d, pos0, inverse,
+           cur_stream());
+}
+
+// rows, F of a packed [.., 2F] gate/up tensor
+static void swiglu_extents(const at::Tensor& gu, int64_t* rows, int64_t* f) {
+  TORCH_CHECK(gu.dim() >= 1 && gu.numel() > 0, "swiglu: empty input");
+  TORCH_CHECK(gu.size(-1) % 16 == 0, "swiglu: the packed width 2F needs "
+              "F % 8 == 0, got ", gu.size(-1));
+  *f = gu.size(-1) / 2;
+  *rows = gu.numel() / gu.size(-1);
+  TORCH_CHECK(*f <= (int64_t(1) << 21), "swiglu: F too large");
+}
+
+// out[rows, F] = silu(gu[:, :F]) * gu[:, F:]
+void swiglu_fwd(at::Tensor out, at::Tensor gu) {
+  int64_t rows, f;
+  const at::Device dev = gu.device();
+  check_llama_bf16(gu, dev, "gu");
+  swiglu_extents(gu, &rows, &f);
+  check_llama_bf16(out, dev, "out");
+  TORCH_CHECK(out.numel() == rows * f, "out must be [rows, F]");
+  epl_swiglu_fwd(out.data_ptr(), gu.data_ptr(), rows, f, cur_stream());
+}
+
+// dgu[rows, 2F]: gate half dy u silu'(g), up half dy silu(g)
+void swiglu_bwd(at::Tensor dgu, at::Tensor dy, at::Tensor gu) {
+  int64_t rows, f;
+  const at::Device dev = gu.device();
+  check_llama_bf16(gu, dev, "gu");
+  swiglu_extents(gu, &rows, &f);
+  check_llama_bf16(dgu, dev, "dgu");
+  check_llama_bf16(dy, dev, "dy");
+  TORCH_CHECK(dgu.numel() == gu.numel(), "dgu must match gu");
+  TORCH_CHECK(dy.numel() == rows * f, "dy must be [rows, F]");
+  epl_swiglu_bwd(dgu.data_ptr(), dy.data_ptr(), gu.data_ptr(), rows, f,
+                 cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -709,4 +879,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("causal"), py::arg("split_dkdv"),
         py::arg("drop_mask"), py::arg("inv_keep"), py::arg("dlse"),
         py::arg("seqlens") = py::none());
+  m.def("rms_norm_fwd", &rms_norm_fwd, py::arg("out"), py::arg("x"),
+        py::arg("res"), py::arg("s"), py::arg("gamma"), py::arg("rstd"),
+        py::arg("eps"));
+  m.def("rms_norm_bwd", &rms_norm_bwd, py::arg("dx"), py::arg("dgamma"),
+        py::arg("dy"), py::arg("s"), py::arg("gamma"), py::arg("rstd"),
+        py::arg("dadd") = py::none());
+  m.def("rope_", &rope_, py::arg("x"), py::arg("cos"), py::arg("sin"),
+        py::arg("pos0"), py::arg("inverse"));
+  m.def("swiglu_fwd", &swiglu_fwd);
+  m.def("swiglu_bwd", &swiglu_bwd);
 }

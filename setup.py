@@ -20,6 +20,7 @@ ext = CUDAExtension(
         "csrc/bindings.hip",
         "csrc/comm/rccl_comm.hip",
         "csrc/kernels/kernels.hip",
+        "csrc/kernels/llama_ops.hip",
         "csrc/kernels/moe.hip",
         "csrc/kernels/moe_router.hip",
         "csrc/kernels/mfma_probe.hip",
