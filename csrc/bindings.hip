@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "kernels/attn_block_order.h"
+
 namespace epl {
 void register_comm(py::module& m);
 }
@@ -51,6 +53,7 @@ void epl_colsum(void*, const void*, float*, int64_t, int64_t, int64_t,
 void run_mfma_probe(const unsigned short*, const unsigned short*, float*,
                     hipStream_t);
 void run_tr_read_probe(short*, short*, int, hipStream_t);
+void run_block_order_probe(int*, int, int, hipStream_t);
 void epl_moe_dispatch_fwd(void*, const void*, const int64_t*,
                           const int64_t*, const int64_t*, int64_t, int64_t,
                           int64_t, hipStream_t);
@@ -506,6 +509,34 @@ void tr_read_probe(at::Tensor out_gather, at::Tensor out_tr,
                     (int)head_dim, cur_stream());
 }
 
+// out: int32 [n * bh, 2] — the (bh, blk) of every block of a non-causal
+// attention grid dim3(n, bh), at its linear id (block_order_probe_kernel)
+void attn_block_order_probe(at::Tensor out, int64_t n, int64_t bh) {
+  check(out, at::kInt, "out");
+  TORCH_CHECK(n >= 1 && n <= 65535 && bh >= 1 && bh <= 65535,
+              "grid dimensions must lie in [1, 65535]");
+  TORCH_CHECK(out.numel() == 2 * n * bh, "out must hold ", 2 * n * bh,
+              " elements");
+  run_block_order_probe(out.data_ptr<int>(), (int)n, (int)bh, cur_stream());
+}
+
+// the same map evaluated on the host (no device needed): int32
+// [n * bh, 2] on the CPU
+at::Tensor attn_block_order_host(int64_t n, int64_t bh) {
+  TORCH_CHECK(n >= 1 && n <= 65535 && bh >= 1 && bh <= 65535,
+              "grid dimensions must lie in [1, 65535]");
+  at::Tensor out = at::empty({n * bh, 2}, at::kInt);
+  int* p = out.data_ptr<int>();
+  for (int64_t y = 0; y < bh; ++y)
+    for (int64_t x = 0; x < n; ++x) {
+      const attn_order::Block b = attn_order::block_of(
+          (unsigned)x, (unsigned)y, (unsigned)n, (unsigned)bh);
+      p[2 * (x + n * y)] = (int)b.bh;
+      p[2 * (x + n * y) + 1] = (int)b.blk;
+    }
+  return out;
+}
+
 void mfma_probe(at::Tensor A, at::Tensor B, at::Tensor D) {
   check(A, at::kBFloat16, "A");
   check(B, at::kBFloat16, "B");
@@ -860,6 +891,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sqnorm", &sqnorm);
   m.def("mfma_probe", &mfma_probe);
   m.def("tr_read_probe", &tr_read_probe);
+  m.def("attn_block_order_probe", &attn_block_order_probe);
+  m.def("attn_block_order_host", &attn_block_order_host);
   m.def("moe_dispatch_fwd", &moe_dispatch_fwd);
   m.def("moe_dispatch_bwd", &moe_dispatch_bwd);
   m.def("moe_combine_fwd", &moe_combine_fwd);

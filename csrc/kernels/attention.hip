@@ -30,17 +30,23 @@
 //
 // Backward: three kernels launched dV -> dQ -> dK (kv-parallel for dV
 // and dK, q-parallel for dQ), each lane owning its output row — no
-// atomics.  The dQ kernel computes D_i = rowsum(dO*O) from the rows it
-// already loads and publishes it for the dK kernel.  64-row q/dO (or
+// atomics; d64 non-causal calls without dropout run dQ -> dK+dV instead,
+// one kv-parallel kernel for both (attn_bwd_dkdv_kernel, same bits;
+// split_dkdv / EPL_ATTN_BWD_SPLIT=1 keep the split pair).  The dQ kernel
+// computes D_i = rowsum(dO*O) from the rows it already loads and
+// publishes it for the dK kernel.  64-row q/dO (or
 // K/V) chunks are staged in one LDS image per tile that is read by rows
 // (ds_read_b128) for S and dP and by columns (ds_read_b64_tr_b16) for
 // dV^T, dK^T and dQ; the dV/dK kernels stage the chunk's -lse/scale and
 // -delta next to it and start the S and dP chains from them.
 // EPL_ATTN_BWD_TILES=legacy selects the previous tile bodies (2-byte
 // LDS gathers, row constants from global memory) for a same-process
-// A/B.  A combined dK+dV kernel (d64, non-causal) stays behind
-// EPL_ATTN_BWD_SPLIT=0.  All kernels take (batch, head, seq) strides so
-// the qkv-unbind views are consumed without copies.
+// A/B.  All kernels take (batch, head, seq) strides so the qkv-unbind
+// views are consumed without copies.
+//
+// Non-causal grids run in the XCD-local block order of
+// attn_block_order.h: the 128-row blocks of a batch-head, which read the
+// same operands, share one L2 instead of fetching them once per XCD.
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -48,6 +54,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "attn_block_order.h"
 #include "attn_lds_image.h"
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
@@ -180,6 +187,24 @@ DEVI int64_t sample_len(const int* seqlens, int64_t b, int64_t seq) {
   if (seqlens == nullptr) return seq;
   const int64_t n = __builtin_amdgcn_readfirstlane(seqlens[b]);
   return n < 0 ? 0 : (n > seq ? seq : n);
+}
+
+// this workgroup's batch-head and 128-row block.  Causal grids carry bh
+// on x and the blocks on y (longest-first packing, see attn_fwd_kernel;
+// `descending`: the q-parallel kernels take their longest block, the
+// last one, first).  Non-causal grids carry the blocks on x and bh on y
+// and take the XCD-local order of attn_block_order.h.  Block-uniform.
+struct BlockPos {
+  int64_t bh, blk;
+};
+DEVI BlockPos block_pos(int causal, bool descending) {
+  if (causal)
+    return {(int64_t)blockIdx.x,
+            descending ? (int64_t)gridDim.y - 1 - blockIdx.y
+                       : (int64_t)blockIdx.y};
+  const attn_order::Block b =
+      attn_order::block_of(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+  return {(int64_t)b.bh, (int64_t)b.blk};
 }
 
 // padded rows are written as exact zeros: one lane's share of an output
@@ -389,11 +414,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
   // reversal still launched one longest block in the LAST row — a
   // ~1-block drain tail that left causal at ~35% packing efficiency
   // at s4096 (profiles/r02_attention_ab.txt wave-residency probe).
-  const int64_t bh = causal ? (int64_t)blockIdx.x : (int64_t)blockIdx.y;
+  // non-causal: the XCD-local order of attn_block_order.h, so that the
+  // q-blocks of a batch-head stream its K and V through one L2
+  const BlockPos pos = block_pos(causal, true);
+  const int64_t bh = pos.bh;
   const int64_t boff = (bh / heads) * in_sb + (bh % heads) * in_sh;
-  const int64_t qb = causal ? (int64_t)gridDim.y - 1 - blockIdx.y
-                            : (int64_t)blockIdx.x;
-  const int64_t q0_blk = qb * 128;
+  const int64_t q0_blk = pos.blk * 128;
   const int64_t q0 = q0_blk + wave * 32;
   const int64_t len = sample_len(seqlens, bh / heads, seq);
   const int64_t myq = q0 + lq;
@@ -551,171 +577,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
 }
 
 // ============================================================================
-// backward: D_i = rowsum(dO * O) precompute
-// ============================================================================
-// ============================================================================
-__global__ void attn_bwd_prep_kernel(const short* __restrict__ dout,
-                                     const short* __restrict__ out,
-                                     float* __restrict__ delta,
-                                     int64_t rows, int64_t seq,
-                                     int64_t heads, int64_t do_sb,
-                                     int64_t do_sh, int64_t do_ss,
-                                     int64_t o_sb, int64_t o_sh,
-                                     int64_t o_ss) {
-  const int lane = threadIdx.x & 63;
-  const int waves_per_block = blockDim.x >> 6;
-  for (int64_t row = (int64_t)blockIdx.x * waves_per_block +
-                     (threadIdx.x >> 6);
-       row < rows; row += (int64_t)gridDim.x * waves_per_block) {
-    const int64_t bh = row / seq;
-    const int64_t sq = row % seq;
-    const short* dp = dout + (bh / heads) * do_sb + (bh % heads) * do_sh +
-                      sq * do_ss;
-    const short* op = out + (bh / heads) * o_sb + (bh % heads) * o_sh +
-                      sq * o_ss;
-    float acc = bf2f(dp[lane]) * bf2f(op[lane]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-      acc += __shfl_down(acc, off, 64);
-    if (lane == 0) delta[row] = acc;
-  }
-}
-
-// ============================================================================
-// backward kernel A (kv-parallel): dK and dV.  One wave per 32-key kv
-// tile, looping q tiles.  Q and dO tiles are staged in LDS as row copies
-// once per block: the row fragments read back as conflict-free
-// ds_read_b128 and the transposed fragments as pair-broadcast 2-byte LDS
-// reads — no global gathers in the loop.
-// ============================================================================
-__global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(
-    const short* __restrict__ q, const short* __restrict__ k,
-    const short* __restrict__ v, const short* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    short* __restrict__ dk, short* __restrict__ dv, int64_t seq,
-    float scale, int causal, int64_t heads, int64_t in_sb, int64_t in_sh,
-    int64_t in_ss, int64_t do_sb, int64_t do_sh, int64_t do_ss,
-    int64_t g_sb, int64_t g_sh, int64_t g_ss) {
-  __shared__ short ldsQ[32][72];
-  __shared__ short ldsDO[32][72];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int hi = lane >> 5;
-  const int lkv = lane & 31;
-  const int64_t bh = blockIdx.y;
-  const int64_t kv0_blk = (int64_t)blockIdx.x * 128;
-  const int64_t kv0 = kv0_blk + wave * 32;
-  const bool active = kv0 < seq;
-  const int64_t boff = (bh / heads) * in_sb + (bh % heads) * in_sh;
-  const short* qp = q + boff;
-  const short* kp = k + boff;
-  const short* vp = v + boff;
-  const short* dop = dout + (bh / heads) * do_sb + (bh % heads) * do_sh;
-  const float* lsep = lse + bh * seq;
-  const float* dltp = delta + bh * seq;
-
-  const int64_t mykv = kv0 + lkv;
-  const int64_t kvrow = mykv < seq ? mykv : seq - 1;
-
-  bf16x8 kfrag[4], vfrag[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    kfrag[c] = *reinterpret_cast<const bf16x8*>(
-        kp + kvrow * in_ss + hi * 8 + 16 * c);
-    vfrag[c] = *reinterpret_cast<const bf16x8*>(
-        vp + kvrow * in_ss + hi * 8 + 16 * c);
-  }
-
-  f32x16 dvt0 = {}, dvt1 = {};
-  f32x16 dkt0 = {}, dkt1 = {};
-
-  const int stage_row = threadIdx.x >> 3;        // 0..31
-  const int stage_seg = (threadIdx.x & 7) * 8;   // 0..56
-  const int64_t q_start = causal ? (kv0_blk / 32) * 32 : 0;
-  for (int64_t q0 = q_start; q0 < seq; q0 += 32) {
-    __syncthreads();
-    {
-      int64_t qr = q0 + stage_row;
-      if (qr >= seq) qr = seq - 1;   // masked rows contribute zero
-      *reinterpret_cast<bf16x8*>(&ldsQ[stage_row][stage_seg]) =
-          *reinterpret_cast<const bf16x8*>(qp + qr * in_ss + stage_seg);
-      *reinterpret_cast<bf16x8*>(&ldsDO[stage_row][stage_seg]) =
-          *reinterpret_cast<const bf16x8*>(dop + qr * do_ss + stage_seg);
-    }
-    __syncthreads();
-    if (!active || (causal && q0 + 31 < kv0)) continue;
-    f32x16 st = {};
-    f32x16 dpt = {};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      bf16x8 qf = *reinterpret_cast<const bf16x8*>(
-          &ldsQ[lkv][hi * 8 + 16 * c]);
-      bf16x8 dof = *reinterpret_cast<const bf16x8*>(
-          &ldsDO[lkv][hi * 8 + 16 * c]);
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfrag[c], st, 0, 0,
-                                                   0);
-      dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vfrag[c], dpt, 0,
-                                                    0, 0);
-    }
-    float p[16], ds[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t qg = q0 + crow(r, hi);
-      const int64_t qgc = qg < seq ? qg : seq - 1;
-      float sv = st[r] * scale;
-      bool masked = qg >= seq || (causal && mykv > qg) || mykv >= seq;
-      float pv = masked ? 0.f : __expf(sv - lsep[qgc]);
-      p[r] = pv;
-      ds[r] = masked ? 0.f : pv * (dpt[r] - dltp[qgc]) * scale;
-    }
-    bf16x8 pb0 = assemble_pfrag(&p[0]);
-    bf16x8 pb1 = assemble_pfrag(&p[8]);
-    bf16x8 db0 = assemble_pfrag(&ds[0]);
-    bf16x8 db1 = assemble_pfrag(&ds[8]);
-#pragma unroll
-    for (int qc = 0; qc < 2; ++qc) {
-      bf16x8 dot0, dot1, qt0, qt1;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int qr = qc * 16 + hi * 8 + j;
-        dot0[j] = ldsDO[qr][lkv];
-        dot1[j] = ldsDO[qr][32 + lkv];
-        qt0[j] = ldsQ[qr][lkv];
-        qt1[j] = ldsQ[qr][32 + lkv];
-      }
-      bf16x8 pb = qc == 0 ? pb0 : pb1;
-      bf16x8 db = qc == 0 ? db0 : db1;
-      dvt0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dot0, pb, dvt0, 0, 0,
-                                                     0);
-      dvt1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dot1, pb, dvt1, 0, 0,
-                                                     0);
-      dkt0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt0, db, dkt0, 0, 0,
-                                                     0);
-      dkt1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt1, db, dkt1, 0, 0,
-                                                     0);
-    }
-  }
-
-  if (!active || mykv >= seq) return;
-  const int64_t goff = (bh / heads) * g_sb + (bh % heads) * g_sh +
-                       mykv * g_ss;
-  short* dkp = dk + goff;
-  short* dvp = dv + goff;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    dvp[crow(r, hi)] = (short)f2bf(dvt0[r]);
-    dvp[32 + crow(r, hi)] = (short)f2bf(dvt1[r]);
-    dkp[crow(r, hi)] = (short)f2bf(dkt0[r]);
-    dkp[32 + crow(r, hi)] = (short)f2bf(dkt1[r]);
-  }
-}
-
-// ============================================================================
-// split backward A kernels: dV-only and dK-only.  Same structure as the
-// combined kernel but half the accumulators each -> 3 waves/SIMD instead
-// of 2 (A/B-selectable via epl_attn_bwd mode).  The q loop runs in three
-// phases: masked causal-diagonal tiles, branch-free bulk tiles, masked
-// seq tail (same rationale as the forward v3 split).
+// backward kernels A (kv-parallel): dV-only and dK-only, one wave per
+// 32-key kv tile, looping 64-row q/dO chunks staged in LDS; half the
+// accumulators of the combined dK+dV kernel further down each -> 3
+// waves/SIMD instead of 2.  The q loop runs in three phases: masked
+// causal-diagonal tiles, branch-free bulk tiles, masked seq tail (same
+// rationale as the forward v3 split).
 // ============================================================================
 
 // one 32-row q sub-tile (of the 64-row staged chunk) of the dV
@@ -980,10 +847,12 @@ void attn_bwd_dv_kernel(
   const int hi = lane >> 5;
   const int lkv = lane & 31;
   // causal: kv0 rides the Y axis (ascending = longest q-range first),
-  // bh on X — global longest-first packing like the fwd kernel
-  const int64_t bh = causal ? (int64_t)blockIdx.x : (int64_t)blockIdx.y;
-  const int64_t kv0_blk =
-      (causal ? (int64_t)blockIdx.y : (int64_t)blockIdx.x) * 128;
+  // bh on X — global longest-first packing like the fwd kernel;
+  // non-causal: XCD-local order, the kv-blocks of a batch-head stream its
+  // Q and dO through one L2
+  const BlockPos pos = block_pos(causal, false);
+  const int64_t bh = pos.bh;
+  const int64_t kv0_blk = pos.blk * 128;
   const int64_t kv0 = kv0_blk + wave * 32;
   const int64_t len = sample_len(seqlens, bh / heads, seq);
   const int64_t mykv = kv0 + lkv;
@@ -1198,9 +1067,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
   const int lkv = lane & 31;
-  const int64_t bh = causal ? (int64_t)blockIdx.x : (int64_t)blockIdx.y;
-  const int64_t kv0_blk =
-      (causal ? (int64_t)blockIdx.y : (int64_t)blockIdx.x) * 128;
+  const BlockPos pos = block_pos(causal, false);   // see attn_bwd_dv_kernel
+  const int64_t bh = pos.bh;
+  const int64_t kv0_blk = pos.blk * 128;
   const int64_t kv0 = kv0_blk + wave * 32;
   const int64_t len = sample_len(seqlens, bh / heads, seq);
   const int64_t mykv = kv0 + lkv;
@@ -1392,6 +1261,208 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 }
 
 // ============================================================================
+// combined dK+dV kernel (d64, non-causal, no dropout): dv_tile_tr and
+// dk_tile_tr on one staged chunk.  Both split tiles compute
+// S' = Q K^T - lse/scale from the same image and take the same 16 exp2;
+// here the tile does that once and the block streams Q and dO once:
+// 16 MFMA per 32x32 tile instead of 8 + 12.  K and V fragments and both
+// accumulator pairs stay in registers, so the kernel runs at 2
+// waves/SIMD.  delta comes from the dQ kernel's workspace: launch order
+// dQ -> dK+dV.
+//
+// Every chain runs in the split tiles' order — S' and dP' from the row
+// constants over c = 0..3, P = exp2(c2 S'), dV^T += dO^T P over (qc, dj),
+// dS = P dP' scale in dk_tile_tr's expression, dK^T += Q^T dS over
+// (qc, dj), chunks and sub-tiles ascending — so dk and dv carry the bits
+// of attn_bwd_dv_kernel / attn_bwd_dk_kernel
+// (tests/test_attention_dkdv_fused_gpu.py).
+// ============================================================================
+template <bool MASKED>
+DEVI void dkdv_tile_tr(const short* imgQ, const short* imgDO,
+                       const float* lseL, const float* dltL, int sub,
+                       int64_t q0, int64_t seq, int64_t mykv, float scale,
+                       const bf16x8 (&kfrag)[4], const bf16x8 (&vfrag)[4],
+                       f32x16 (&dvt)[2], f32x16 (&dkt)[2], int lkv, int hi) {
+  constexpr int D = 64;
+  f32x16 st = load_rowconst(lseL, hi);
+  f32x16 dpt = load_rowconst(dltL, hi);
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) {
+    const int o = img_off<D>(sub + lkv, 2 * c + hi);
+    bf16x8 qf = *reinterpret_cast<const bf16x8*>(imgQ + o);
+    bf16x8 dof = *reinterpret_cast<const bf16x8*>(imgDO + o);
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfrag[c], st, 0, 0, 0);
+    dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vfrag[c], dpt, 0, 0,
+                                                  0);
+  }
+  const float c2 = scale * 1.44269504088896341f;   // P = exp2(c2 * S')
+  const RowMask rm(q0, seq, mykv, 0);
+  float p[16], ds[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float e = __builtin_amdgcn_exp2f(st[r] * c2);
+    if (MASKED) {
+      const bool m = rm.masked(crow(r, hi));
+      p[r] = m ? 0.f : e;
+      ds[r] = m ? 0.f : e * dpt[r] * scale;
+    } else {
+      p[r] = e;
+      ds[r] = e * dpt[r] * scale;
+    }
+  }
+  const int lane = hi * 32 + lkv;
+  bf16x8 pb0 = assemble_pfrag<true>(&p[0]);
+  bf16x8 pb1 = assemble_pfrag<true>(&p[8]);
+#pragma unroll
+  for (int qc = 0; qc < 2; ++qc) {
+    bf16x8 pb = qc == 0 ? pb0 : pb1;
+#pragma unroll
+    for (int dj = 0; dj < D / 32; ++dj) {
+      bf16x8 dot = tr_frag<D>(imgDO, sub + qc * 16, dj, lane);
+      dvt[dj] =
+          __builtin_amdgcn_mfma_f32_32x32x16_bf16(dot, pb, dvt[dj], 0, 0, 0);
+    }
+  }
+  bf16x8 db0 = assemble_pfrag<true>(&ds[0]);
+  bf16x8 db1 = assemble_pfrag<true>(&ds[8]);
+#pragma unroll
+  for (int qc = 0; qc < 2; ++qc) {
+    bf16x8 db = qc == 0 ? db0 : db1;
+#pragma unroll
+    for (int dj = 0; dj < D / 32; ++dj) {
+      bf16x8 qt = tr_frag<D>(imgQ, sub + qc * 16, dj, lane);
+      dkt[dj] =
+          __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt, db, dkt[dj], 0, 0, 0);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(
+    const short* __restrict__ q, const short* __restrict__ k,
+    const short* __restrict__ v, const short* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    short* __restrict__ dk, short* __restrict__ dv, int64_t seq,
+    float scale, int64_t heads, int64_t in_sb, int64_t in_sh,
+    int64_t in_ss, int64_t do_sb, int64_t do_sh, int64_t do_ss,
+    int64_t g_sb, int64_t g_sh, int64_t g_ss,
+    const int* __restrict__ seqlens) {
+  constexpr int D = 64;
+  __shared__ __attribute__((aligned(16))) short ldsQ[2][64][img_pitch<D>()];
+  __shared__ __attribute__((aligned(16))) short ldsDO[2][64][img_pitch<D>()];
+  // [0] = -lse/scale, [1] = -delta of the chunk's 64 rows
+  __shared__ __attribute__((aligned(16))) float ldsL[2][2][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int hi = lane >> 5;
+  const int lkv = lane & 31;
+  const BlockPos pos = block_pos(0, false);   // see attn_bwd_dv_kernel
+  const int64_t bh = pos.bh;
+  const int64_t kv0_blk = pos.blk * 128;
+  const int64_t kv0 = kv0_blk + wave * 32;
+  const int64_t len = sample_len(seqlens, bh / heads, seq);
+  const int64_t mykv = kv0 + lkv;
+  const int64_t goff = (bh / heads) * g_sb + (bh % heads) * g_sh +
+                       mykv * g_ss;
+  // padded key rows are zeroed ahead of the loop and a block wholly
+  // inside the padding loads nothing (see attn_fwd_kernel)
+  if (mykv >= len && mykv < seq) {
+    zero_row<D>(dk + goff, hi);
+    zero_row<D>(dv + goff, hi);
+  }
+  if (kv0_blk >= len) return;
+  const bool active = kv0 < len;
+  const int64_t boff = (bh / heads) * in_sb + (bh % heads) * in_sh;
+  const short* qp = q + boff;
+  const short* kp = k + boff;
+  const short* vp = v + boff;
+  const short* dop = dout + (bh / heads) * do_sb + (bh % heads) * do_sh;
+  const float* lsep = lse + bh * seq;
+  const float* dltp = delta + bh * seq;
+
+  const int64_t kvrow = mykv < len ? mykv : len - 1;
+  bf16x8 kfrag[D / 16], vfrag[D / 16];
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) {
+    kfrag[c] = *reinterpret_cast<const bf16x8*>(
+        kp + kvrow * in_ss + hi * 8 + 16 * c);
+    vfrag[c] = *reinterpret_cast<const bf16x8*>(
+        vp + kvrow * in_ss + hi * 8 + 16 * c);
+  }
+
+  f32x16 dvt[D / 32] = {};
+  f32x16 dkt[D / 32] = {};
+  const int stage_row = threadIdx.x >> 3;
+  const int stage_seg = (threadIdx.x & 7) * 8;
+
+  // the dV kernel's register-double-buffered single-barrier staging,
+  // carrying the dK kernel's two row constants (wave 0 -lse/scale,
+  // wave 1 -delta)
+  bf16x8 rq[2], rdo[2];
+  float rl = 0.f;
+  const float neg_inv_scale = -1.f / scale;
+  auto prefetch = [&](int64_t q0) {
+    if (wave < 2) {
+      const int64_t qr = q0 + lane;
+      rl = (wave == 0 ? lsep : dltp)[qr < len ? qr : len - 1] *
+           (wave == 0 ? neg_inv_scale : -1.f);
+    }
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      int64_t qr = q0 + stage_row + half * 32;
+      if (qr >= len) qr = len - 1;
+      rq[half] = *reinterpret_cast<const bf16x8*>(qp + qr * in_ss +
+                                                  stage_seg);
+      rdo[half] = *reinterpret_cast<const bf16x8*>(dop + qr * do_ss +
+                                                   stage_seg);
+    }
+  };
+  auto commit = [&](int buf) {
+    if (wave < 2) ldsL[buf][wave][lane] = rl;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int o = img_off<D>(stage_row + half * 32, stage_seg >> 3);
+      *reinterpret_cast<bf16x8*>(&ldsQ[buf][0][0] + o) = rq[half];
+      *reinterpret_cast<bf16x8*>(&ldsDO[buf][0][0] + o) = rdo[half];
+    }
+  };
+
+  const int64_t bulk_end = len & ~(int64_t)63;
+  int buf = 0;
+  prefetch(0);
+  for (int64_t q0 = 0; q0 < len; q0 += 64) {
+    commit(buf);
+    __syncthreads();
+    if (q0 + 64 < len) prefetch(q0 + 64);
+    const int rb = buf;
+    buf ^= 1;
+    const short* imgQ = &ldsQ[rb][0][0];
+    const short* imgDO = &ldsDO[rb][0][0];
+    if (q0 + 63 < bulk_end) {
+#pragma unroll
+      for (int sub = 0; sub < 64; sub += 32)
+        dkdv_tile_tr<false>(imgQ, imgDO, &ldsL[rb][0][sub],
+                            &ldsL[rb][1][sub], sub, q0 + sub, len, mykv,
+                            scale, kfrag, vfrag, dvt, dkt, lkv, hi);
+    } else if (active) {
+#pragma unroll
+      for (int sub = 0; sub < 64; sub += 32) {
+        const int64_t q0s = q0 + sub;
+        if (q0s >= len) break;
+        dkdv_tile_tr<true>(imgQ, imgDO, &ldsL[rb][0][sub],
+                           &ldsL[rb][1][sub], sub, q0s, len, mykv, scale,
+                           kfrag, vfrag, dvt, dkt, lkv, hi);
+      }
+    }
+  }
+  if (!active || mykv >= len) return;
+#pragma unroll
+  for (int dj = 0; dj < D / 32; ++dj) {
+    store_acc_bf16(dv + goff + dj * 32, dvt[dj], hi);
+    store_acc_bf16(dk + goff + dj * 32, dkt[dj], hi);
+  }
+}
+
+// ============================================================================
 // backward kernel B (q-parallel): dQ.  K and V tiles staged in LDS as
 // row copies per block; row fragments via ds_read_b128, K-transposed
 // fragments via 2-byte LDS reads.  Like the forward, the kv loop is
@@ -1538,11 +1609,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
   const int lq = lane & 31;
-  // causal: global longest-first packing (see attn_fwd_kernel)
-  const int64_t bh = causal ? (int64_t)blockIdx.x : (int64_t)blockIdx.y;
-  const int64_t qb = causal ? (int64_t)gridDim.y - 1 - blockIdx.y
-                            : (int64_t)blockIdx.x;
-  const int64_t q0_blk = qb * 128;
+  // causal: global longest-first packing; non-causal: XCD-local order
+  // (see attn_fwd_kernel)
+  const BlockPos pos = block_pos(causal, true);
+  const int64_t bh = pos.bh;
+  const int64_t q0_blk = pos.blk * 128;
   const int64_t q0 = q0_blk + wave * 32;
   const int64_t len = sample_len(seqlens, bh / heads, seq);
   const int64_t myq = q0 + lq;
@@ -1786,21 +1857,19 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
                   const unsigned int* drop_mask, int64_t mask_w,
                   float inv_keep, int64_t head_dim, const float* dlse,
                   const int* seqlens, hipStream_t stream) {
-  const int64_t rows = batch_heads * seq;
   const unsigned nqb = (unsigned)((seq + 127) / 128);
   dim3 grid = causal ? dim3((unsigned)batch_heads, nqb)
                      : dim3(nqb, (unsigned)batch_heads);
-  // head_dim 128 and causal always run the split kernels (the combined
-  // dkdv kernel is d=64-only and keeps the legacy x-major grid)
-  // per-sample lengths run the split kernels too (the combined kernel
-  // and its prep pass know no padding)
-  if (split_dkdv || drop_mask != nullptr || head_dim == 128 || causal ||
-      dlse != nullptr || seqlens != nullptr) {
-    // order: dV (needs no delta) -> dQ (computes + publishes delta from
-    // the dO/O rows it already loads) -> dK (consumes delta).  The prep
-    // pass disappears.  Dropout always runs the split kernels (the
-    // combined dkdv kernel has no mask path).
-#define DV_ARGS                                                          \
+  // split_dkdv = 0 asks for the combined dK+dV kernel; it exists for d64,
+  // non-causal, no dropout (with or without seqlens and dlse), and every
+  // other call runs the split kernels whatever the flag says.
+  const bool fused = !split_dkdv && drop_mask == nullptr &&
+                     head_dim == 64 && !causal;
+  {
+    // split order: dV (needs no delta) -> dQ (computes + publishes delta
+    // from the dO/O rows it already loads) -> dK (consumes delta).
+    // Combined: dQ -> dK+dV.
+#define DV_ARGS                                                         \
   reinterpret_cast<const short*>(q), reinterpret_cast<const short*>(k),  \
       reinterpret_cast<const short*>(dout), lse,                         \
       reinterpret_cast<short*>(dv), seq, scale, causal ? 1 : 0, heads,   \
@@ -1854,7 +1923,9 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
       constexpr bool DROP = decltype(drop_c)::value;
       constexpr int D = decltype(d_c)::value;
       constexpr bool TR = decltype(tr_c)::value;
-      if (D == 64 && dbuf)
+      if (fused) {
+        // nothing to launch ahead of dQ
+      } else if (D == 64 && dbuf)
         hipLaunchKernelGGL(
             HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, D == 64, D, TR>), grid,
             dim3(256), 0, stream, DV_ARGS);
@@ -1870,7 +1941,18 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
         hipLaunchKernelGGL(
             HIP_KERNEL_NAME(attn_bwd_dq_kernel<DROP, false, D, TR>), grid,
             dim3(256), 0, stream, DQ_ARGS);
-      if (D == 64 && dbuf_k)
+      if (fused)
+        hipLaunchKernelGGL(
+            attn_bwd_dkdv_kernel, grid, dim3(256), 0, stream,
+            reinterpret_cast<const short*>(q),
+            reinterpret_cast<const short*>(k),
+            reinterpret_cast<const short*>(v),
+            reinterpret_cast<const short*>(dout), lse, delta_ws,
+            reinterpret_cast<short*>(dk), reinterpret_cast<short*>(dv), seq,
+            scale, heads, in_strides[0], in_strides[1], in_strides[2],
+            do_strides[0], do_strides[1], do_strides[2], g_strides[0],
+            g_strides[1], g_strides[2], seqlens);
+      else if (D == 64 && dbuf_k)
         hipLaunchKernelGGL(
             HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, D == 64, D, TR>), grid,
             dim3(256), 0, stream, DK_ARGS);
@@ -1900,47 +1982,7 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
 #undef DV_ARGS
 #undef DQ_ARGS
 #undef DK_ARGS
-    return;
   }
-  {
-    const int64_t blocks = (rows + 3) / 4;
-    hipLaunchKernelGGL(attn_bwd_prep_kernel,
-                       dim3((unsigned)(blocks < 4096 ? blocks : 4096)),
-                       dim3(256), 0, stream,
-                       reinterpret_cast<const short*>(dout),
-                       reinterpret_cast<const short*>(out), delta_ws, rows,
-                       seq, heads, do_strides[0], do_strides[1],
-                       do_strides[2], o_strides[0], o_strides[1],
-                       o_strides[2]);
-  }
-  hipLaunchKernelGGL(attn_bwd_dkdv_kernel, grid, dim3(256), 0, stream,
-                     reinterpret_cast<const short*>(q),
-                     reinterpret_cast<const short*>(k),
-                     reinterpret_cast<const short*>(v),
-                     reinterpret_cast<const short*>(dout), lse, delta_ws,
-                     reinterpret_cast<short*>(dk),
-                     reinterpret_cast<short*>(dv), seq, scale,
-                     causal ? 1 : 0, heads, in_strides[0], in_strides[1],
-                     in_strides[2], do_strides[0], do_strides[1],
-                     do_strides[2], g_strides[0], g_strides[1],
-                     g_strides[2]);
-  // the combined dK+dV kernel keeps its own body; its dQ partner runs
-  // the new tiles (a legacy A/B goes through the split path above)
-  hipLaunchKernelGGL(
-      HIP_KERNEL_NAME(attn_bwd_dq_kernel<false, false, 64, true>),
-                     grid, dim3(256), 0, stream,
-                     reinterpret_cast<const short*>(q),
-                     reinterpret_cast<const short*>(k),
-                     reinterpret_cast<const short*>(v),
-                     reinterpret_cast<const short*>(dout), lse, delta_ws,
-                     reinterpret_cast<short*>(dq),
-                     reinterpret_cast<const short*>(out), seq, scale,
-                     causal ? 1 : 0, heads, in_strides[0], in_strides[1],
-                     in_strides[2], do_strides[0], do_strides[1],
-                     do_strides[2], g_strides[0], g_strides[1],
-                     g_strides[2], o_strides[0], o_strides[1],
-                     o_strides[2], drop_mask, mask_w, inv_keep, dlse,
-                     (const int*)nullptr);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "attn_block_order.h"
 #include "attn_lds_image.h"
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
@@ -81,4 +82,22 @@ extern "C" void run_tr_read_probe(short* out_gather, short* out_tr,
   else
     hipLaunchKernelGGL(tr_read_probe_kernel<64>, dim3(1), dim3(64), 0,
                        stream, out_gather, out_tr);
+}
+
+// Block-order probe: launched on a non-causal attention grid dim3(n, BH),
+// every block writes the (bh, blk) that attn_order::block_of gives it at
+// its linear id L = blockIdx.x + n * blockIdx.y.  out: int32 [n * BH][2].
+__global__ void block_order_probe_kernel(int* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  const attn_order::Block b =
+      attn_order::block_of(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
+  const unsigned int L = blockIdx.x + gridDim.x * blockIdx.y;
+  out[2 * (size_t)L] = (int)b.bh;
+  out[2 * (size_t)L + 1] = (int)b.blk;
+}
+
+extern "C" void run_block_order_probe(int* out, int n, int bh,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(block_order_probe_kernel, dim3(n, bh), dim3(64), 0,
+                     stream, out);
 }

@@ -18,6 +18,8 @@ and clamp the lengths themselves (no host sync), skip the padded tiles
 and exit whole blocks past the length.
 """
 
+import os
+
 import torch
 import torch.nn.functional as F
 
@@ -82,6 +84,15 @@ def _mask_tensor(b, h, seq, device):
                        device=device)
 
 
+def _bwd_split():
+    """The ``split_dkdv`` flag of ``attn_bwd``.  Default: the combined
+    dK+dV kernel (one Q/dO stream, one exp pass) wherever it exists —
+    d64, non-causal, no dropout; every other call runs the split kernels
+    whatever the flag says.  EPL_ATTN_BWD_SPLIT=1 asks for the split
+    dV and dK kernels everywhere; both give the same bits."""
+    return os.environ.get("EPL_ATTN_BWD_SPLIT", "0") == "1"
+
+
 def _saved_optionals(ctx, rest):
     """(mask, seqlens) from the tail of the saved tensors"""
     rest = list(rest)
@@ -124,7 +135,6 @@ class _FlashAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        import os
         saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
         q, k, v, out, lse = saved[:5]
         mask, seqlens = _saved_optionals(ctx, saved[5:])
@@ -149,11 +159,8 @@ class _FlashAttention(torch.autograd.Function):
         dk = grad_like(orig_q)
         dv = grad_like(orig_q)
         delta = torch.empty_like(lse)
-        # split dK/dV kernels measure ~4% faster than the combined one
-        # (3 vs 2 waves/SIMD; A/B in profiles/r01_attention_ab.txt)
-        split = os.environ.get("EPL_ATTN_BWD_SPLIT", "1") == "1"
         native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv,
-                              ctx.scale, ctx.causal, split, mask,
+                              ctx.scale, ctx.causal, _bwd_split(), mask,
                               ctx.inv_keep, None, seqlens)
         return dq, dk, dv, None, None, None, None
 
@@ -204,7 +211,7 @@ class _QKVFlashAttention(torch.autograd.Function):
         dv = dqkv[:, :, 2].transpose(1, 2)
         delta = torch.empty_like(lse)
         native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv,
-                              ctx.scale, ctx.causal, True, mask,
+                              ctx.scale, ctx.causal, _bwd_split(), mask,
                               ctx.inv_keep, None, seqlens)
         return dqkv, None, None, None, None
 
