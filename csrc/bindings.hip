@@ -113,6 +113,18 @@ void check(const at::Tensor& t, at::ScalarType dtype, const char* name) {
               ", expected ", dtype);
 }
 
+// cuda + contiguous, dtype bf16 or fp32 (returned by is_bf16)
+void check_arena(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a device tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// the vector loads and stores of the arena kernels start at the base
+void check_aligned(const at::Tensor& t, size_t bytes, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0, name,
+              " must start on a ", bytes, "-byte boundary");
+}
+
 bool is_bf16(const at::Tensor& t) {
   TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat,
               "expected bf16 or fp32, got ", t.scalar_type());
@@ -126,16 +138,24 @@ void fused_adamw(at::Tensor master, c10::optional<at::Tensor> param_bf16,
   check(master, at::kFloat, "master");
   check(m, at::kFloat, "m");
   check(v, at::kFloat, "v");
+  check_arena(grad, "grad");
   const bool gbf = is_bf16(grad);
   unsigned short* pb = nullptr;
   if (param_bf16.has_value()) {
     check(*param_bf16, at::kBFloat16, "param_bf16");
-    TORCH_CHECK(param_bf16->numel() == master.numel());
+    TORCH_CHECK(param_bf16->numel() == master.numel(),
+                "arena size mismatch");
+    check_aligned(*param_bf16, 16, "param_bf16");
     pb = reinterpret_cast<unsigned short*>(param_bf16->data_ptr());
   }
   const int64_t n = master.numel();
   TORCH_CHECK(grad.numel() == n && m.numel() == n && v.numel() == n,
               "arena size mismatch");
+  // eight elements per access: 32 bytes of fp32, 16 of bf16
+  check_aligned(master, 32, "master");
+  check_aligned(m, 32, "m");
+  check_aligned(v, 32, "v");
+  check_aligned(grad, gbf ? 16 : 32, "grad");
   epl_fused_adamw(master.data_ptr<float>(), pb, grad.data_ptr(), gbf,
                   m.data_ptr<float>(), v.data_ptr<float>(), n, (float)lr,
                   (float)beta1, (float)beta2, (float)eps, (float)weight_decay,
@@ -348,7 +368,9 @@ void ce_backward(at::Tensor dlogits, at::Tensor logits, at::Tensor targets,
 }
 
 void scale_(at::Tensor t, double s) {
+  check_arena(t, "t");
   const bool bf16 = is_bf16(t);
+  check_aligned(t, 16, "t");   // float4 / bf16x8 accesses
   epl_scale(t.data_ptr(), t.numel(), (float)s, bf16, cur_stream());
 }
 
@@ -356,6 +378,8 @@ void f32_to_bf16(at::Tensor dst, at::Tensor src) {
   check(dst, at::kBFloat16, "dst");
   check(src, at::kFloat, "src");
   TORCH_CHECK(dst.numel() == src.numel());
+  check_aligned(dst, 16, "dst");   // bf16x8 stores, float4 loads
+  check_aligned(src, 16, "src");
   epl_f32_to_bf16(reinterpret_cast<unsigned short*>(dst.data_ptr()),
                   src.data_ptr<float>(), src.numel(), cur_stream());
 }
@@ -364,6 +388,8 @@ void bf16_to_f32(at::Tensor dst, at::Tensor src) {
   check(dst, at::kFloat, "dst");
   check(src, at::kBFloat16, "src");
   TORCH_CHECK(dst.numel() == src.numel());
+  check_aligned(dst, 16, "dst");   // float4 stores, bf16x8 loads
+  check_aligned(src, 16, "src");
   epl_bf16_to_f32(dst.data_ptr<float>(),
                   reinterpret_cast<unsigned short*>(src.data_ptr()),
                   src.numel(), cur_stream());
@@ -702,8 +728,10 @@ void colsum(at::Tensor dy, at::Tensor db, at::Tensor partial) {
 }
 
 void sqnorm(at::Tensor t, at::Tensor out) {
+  check_arena(t, "t");   // element loads: no alignment beyond the dtype's
   const bool bf16 = is_bf16(t);
   check(out, at::kFloat, "out");
+  TORCH_CHECK(out.numel() >= 1, "out must hold one element");
   epl_sqnorm(t.data_ptr(), t.numel(), out.data_ptr<float>(), bf16,
              cur_stream());
 }

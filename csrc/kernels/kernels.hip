@@ -31,12 +31,20 @@ DEV float bf2f(unsigned short u) {
   return __uint_as_float(x);
 }
 
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16v2 = __attribute__((ext_vector_type(2))) __bf16;
+
+// two floats -> packed bf16 pair in one v_cvt_pk_bf16_f32: round to
+// nearest even, and a NaN stays a NaN
+DEV unsigned int cvt_pk_bf16(float a, float b) {
+  f32x2 f = {a, b};
+  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f, bf16v2));
+}
+
 DEV unsigned short f2bf(float f) {
-  // round-to-nearest-even bf16 conversion
-  unsigned int x = __float_as_uint(f);
-  unsigned int lsb = (x >> 16) & 1u;
-  x += 0x7fffu + lsb;
-  return (unsigned short)(x >> 16);
+  // the hardware convert, not the integer rounding add x + 0x7fff + lsb:
+  // that add carries a NaN with a full high mantissa half into +-0 or Inf
+  return (unsigned short)cvt_pk_bf16(f, f);
 }
 
 struct ushort8 {
@@ -55,10 +63,9 @@ DEV float8 load_bf16x8(const unsigned short* p) {
 }
 
 DEV void store_bf16x8(unsigned short* p, const float8& f) {
-  ushort8 raw;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) raw.v[i] = f2bf(f.v[i]);
-  *reinterpret_cast<ushort8*>(p) = raw;
+  *reinterpret_cast<uint4*>(p) =
+      make_uint4(cvt_pk_bf16(f.v[0], f.v[1]), cvt_pk_bf16(f.v[2], f.v[3]),
+                 cvt_pk_bf16(f.v[4], f.v[5]), cvt_pk_bf16(f.v[6], f.v[7]));
 }
 
 DEV float8 load_f32x8(const float* p) {
@@ -79,6 +86,13 @@ DEV void store_f32x8(float* p, const float8& f) {
 inline int grid_for(int64_t work_items) {
   int64_t blocks = (work_items + kBlock - 1) / kBlock;
   return (int)(blocks < kMaxGrid ? (blocks > 0 ? blocks : 1) : kMaxGrid);
+}
+
+// 1 / (1 - beta^step) of the fp32 beta the kernels use, in double and
+// rounded once: in fp32 the subtraction amplifies powf's rounding by
+// beta^step / (1 - beta^step), about 100 ulp at beta 0.999 and steps 2-5
+inline float inv_bias_correction(float beta, int step) {
+  return (float)(1.0 / (1.0 - std::pow((double)beta, (double)step)));
 }
 
 // ---- block-wide reduction (256 threads = 4 waves) ---------------------------
@@ -701,16 +715,6 @@ DEV float gelu_grad_lean(float x) {
   return s + x * s * (1.f - s) * (d0 + d1 * x * x);
 }
 
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16v2 = __attribute__((ext_vector_type(2))) __bf16;
-
-// two floats -> packed bf16 pair in one v_cvt_pk_bf16_f32 (the same
-// round-to-nearest-even as f2bf for finite values)
-DEV unsigned int cvt_pk_bf16(float a, float b) {
-  f32x2 f = {a, b};
-  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f, bf16v2));
-}
-
 DEV void store_bf16x8_pk(unsigned short* p, const float8& f) {
   *reinterpret_cast<uint4*>(p) =
       make_uint4(cvt_pk_bf16(f.v[0], f.v[1]), cvt_pk_bf16(f.v[2], f.v[3]),
@@ -1154,8 +1158,8 @@ void epl_fused_adamw(float* master, unsigned short* param_bf16,
                      int64_t n, float lr, float beta1, float beta2, float eps,
                      float weight_decay, int step, float inv_scale,
                      hipStream_t stream) {
-  const float inv_bias1 = 1.f / (1.f - powf(beta1, (float)step));
-  const float inv_bias2 = 1.f / (1.f - powf(beta2, (float)step));
+  const float inv_bias1 = inv_bias_correction(beta1, step);
+  const float inv_bias2 = inv_bias_correction(beta2, step);
   const int grid = grid_for((n + 7) / 8);
   if (grad_bf16) {
     if (param_bf16)
@@ -1187,8 +1191,8 @@ void epl_lamb_phase1(const float* master, const void* grad, bool grad_bf16,
                      float* wnorm_sq, float* unorm_sq, int64_t n, float beta1,
                      float beta2, float eps, float weight_decay, int step,
                      float inv_scale, hipStream_t stream) {
-  const float inv_bias1 = 1.f / (1.f - powf(beta1, (float)step));
-  const float inv_bias2 = 1.f / (1.f - powf(beta2, (float)step));
+  const float inv_bias1 = inv_bias_correction(beta1, step);
+  const float inv_bias2 = inv_bias_correction(beta2, step);
   const int grid = grid_for(n);
   hipLaunchKernelGGL(lamb_phase1_kernel, dim3(grid), dim3(kBlock), 0, stream,
                      master, grad, grad_bf16, m, v, update, chunk_of, wnorm_sq,
