@@ -25,22 +25,24 @@ void epl_lamb_phase2(float*, unsigned short*, const float*, const int*,
 void epl_layer_norm_fwd(void*, const void*, const void*, void*, const void*,
                         const void*, float*, float*, int64_t, int64_t, float,
                         bool, hipStream_t);
+int64_t epl_layer_norm_bwd_parts(int64_t);
 void epl_layer_norm_bwd(void*, float*, float*, const void*, const void*,
                         const void*, const float*, const float*, float*,
-                        float*, int64_t, int64_t, int64_t, bool,
-                        hipStream_t);
-void epl_layer_norm_bwd_fused(void*, float*, float*, float*, const void*,
+                        float*, int64_t, int64_t, bool, hipStream_t);
+void epl_layer_norm_bwd_fused(void*, void*, void*, void*, int, int, int,
                               const void*, const void*, const void*,
-                              const float*, const float*, float*, float*,
-                              float*, int64_t, int64_t, int64_t, bool,
-                              hipStream_t);
+                              const void*, const void*, const float*,
+                              const float*, float*, float*, float*, int64_t,
+                              int64_t, bool, hipStream_t);
 void epl_bias_gelu_fwd(void*, const void*, const void*, int64_t, int64_t,
                        bool, hipStream_t);
-void epl_bias_gelu_bwd(void*, float*, const void*, const void*, const void*,
-                       float*, int64_t, int64_t, int64_t, bool,
+int64_t epl_bias_gelu_bwd_parts(int64_t);
+void epl_bias_gelu_bwd(void*, void*, int, const void*, const void*,
+                       const void*, float*, int64_t, int64_t, bool,
                        hipStream_t);
 void epl_ce_rowstats(const void*, const int64_t*, float*, float*, float*,
-                     int64_t, int64_t, int64_t, int64_t, bool, hipStream_t);
+                     int64_t, int64_t, int64_t, int64_t, bool, bool,
+                     hipStream_t);
 void epl_ce_backward(void*, const void*, const int64_t*, const float*,
                      const float*, const float*, int64_t, int64_t, int64_t,
                      int64_t, float, bool, hipStream_t);
@@ -218,6 +220,16 @@ void layer_norm_fwd(at::Tensor out, at::Tensor x,
                      cols, (float)eps, bf16, cur_stream());
 }
 
+// how a reducer leaves an output: the values of kernels.hip's kRed* enum
+constexpr int kAccF32 = 0;     // += into pre-zeroed fp32 (older bindings)
+
+// 1 = store fp32, 2 = store bf16 (rounded once), by the tensor's dtype
+int store_mode(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a device tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  return is_bf16(t) ? 2 : 1;
+}
+
 void layer_norm_bwd(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
                     at::Tensor dy, at::Tensor x, at::Tensor gamma,
                     at::Tensor mean, at::Tensor rstd) {
@@ -233,10 +245,8 @@ void layer_norm_bwd(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
   float* dbp = nullptr;
   at::Tensor ws;
   const bool fast = bf16 && cols % 8 == 0 && cols <= 2048;
-  int64_t nparts = 0;
   if (fast) {
-    const int64_t wave_rows = (rows + 3) / 4;
-    nparts = (wave_rows < 1024 ? wave_rows : 1024) * 4;
+    const int64_t nparts = epl_layer_norm_bwd_parts(rows);
     ws = at::empty({2, nparts, cols}, dgamma.options());
     dgp = ws.data_ptr<float>();
     dbp = dgp + nparts * cols;
@@ -244,8 +254,89 @@ void layer_norm_bwd(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
   epl_layer_norm_bwd(dx.data_ptr(), dgamma.data_ptr<float>(),
                      dbeta.data_ptr<float>(), dy.data_ptr(), x.data_ptr(),
                      gamma.data_ptr(), mean.data_ptr<float>(),
-                     rstd.data_ptr<float>(), dgp, dbp, nparts, rows, cols,
-                     bf16, cur_stream());
+                     rstd.data_ptr<float>(), dgp, dbp, rows, cols, bf16,
+                     cur_stream());
+}
+
+// The fused LN backward behind layer_norm_bwd_fused (accumulate = true:
+// fp32 outputs, zero-initialised by the caller, any shape) and
+// layer_norm_bwd_typed (accumulate = false: outputs written in their own
+// dtype, bf16 fast path only).
+void ln_bwd_fused_impl(at::Tensor& dx, at::Tensor& dgamma, at::Tensor& dbeta,
+                       at::Tensor& dy, at::Tensor& x, at::Tensor& gamma,
+                       at::Tensor& mean, at::Tensor& rstd,
+                       c10::optional<at::Tensor>& dadd,
+                       c10::optional<at::Tensor>& colsum_out,
+                       c10::optional<at::Tensor>& dy2, bool accumulate,
+                       const char* who) {
+  const bool bf16 = is_bf16(x);
+  const int64_t cols = x.size(-1);
+  const int64_t rows = x.numel() / cols;
+  TORCH_CHECK(!bf16 || cols % 8 == 0, "bf16 LayerNorm needs cols % 8 == 0");
+  TORCH_CHECK((size_t)cols * 2 * sizeof(float) <= 128 * 1024,
+              "LayerNorm backward supports cols <= 16384");
+  int mode_g = kAccF32, mode_b = kAccF32, mode_c = kAccF32;
+  if (accumulate) {
+    check(dgamma, at::kFloat, "dgamma");
+    check(dbeta, at::kFloat, "dbeta");
+  } else {
+    mode_g = store_mode(dgamma, "dgamma");
+    mode_b = store_mode(dbeta, "dbeta");
+  }
+  check(dx, x.scalar_type(), "dx");
+  check(dy, x.scalar_type(), "dy");
+  check(x, x.scalar_type(), "x");
+  check(gamma, x.scalar_type(), "gamma");
+  check(mean, at::kFloat, "mean");
+  check(rstd, at::kFloat, "rstd");
+  TORCH_CHECK(dx.numel() == x.numel() && dy.numel() == x.numel());
+  TORCH_CHECK(dgamma.numel() == cols && dbeta.numel() == cols);
+  TORCH_CHECK(gamma.numel() == cols && mean.numel() == rows &&
+              rstd.numel() == rows);
+  const bool fast = bf16 && cols % 8 == 0 && cols <= 2048;
+  const bool fused =
+      dadd.has_value() || colsum_out.has_value() || dy2.has_value();
+  TORCH_CHECK(fast || (!fused && accumulate), who,
+              ": dadd / colsum_out / dy2 / typed outputs need the bf16 fast "
+              "path (cols % 8 == 0, cols <= 2048)");
+  const void* dadd_p = nullptr;
+  const void* dy2_p = nullptr;
+  void* cs_out = nullptr;
+  if (dadd.has_value()) {
+    check(*dadd, x.scalar_type(), "dadd");
+    TORCH_CHECK(dadd->numel() == x.numel(), "dadd shape mismatch");
+    dadd_p = dadd->data_ptr();
+  }
+  if (dy2.has_value()) {
+    check(*dy2, x.scalar_type(), "dy2");
+    TORCH_CHECK(dy2->numel() == x.numel(), "dy2 shape mismatch");
+    dy2_p = dy2->data_ptr();
+  }
+  if (colsum_out.has_value()) {
+    if (accumulate)
+      check(*colsum_out, at::kFloat, "colsum_out");
+    else
+      mode_c = store_mode(*colsum_out, "colsum_out");
+    TORCH_CHECK(colsum_out->numel() == cols, "colsum_out shape mismatch");
+    cs_out = colsum_out->data_ptr();
+  }
+  float* dgp = nullptr;
+  float* dbp = nullptr;
+  float* csp = nullptr;
+  at::Tensor ws;
+  if (fast) {
+    const int64_t nparts = epl_layer_norm_bwd_parts(rows);
+    ws = at::empty({cs_out ? 3 : 2, nparts, cols},
+                   x.options().dtype(at::kFloat));
+    dgp = ws.data_ptr<float>();
+    dbp = dgp + nparts * cols;
+    if (cs_out) csp = dbp + nparts * cols;
+  }
+  epl_layer_norm_bwd_fused(dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                           cs_out, mode_g, mode_b, mode_c, dy.data_ptr(),
+                           dy2_p, x.data_ptr(), gamma.data_ptr(), dadd_p,
+                           mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                           dgp, dbp, csp, rows, cols, bf16, cur_stream());
 }
 
 // layer_norm_bwd plus two optional in-kernel fusions on the bf16 fast path
@@ -259,52 +350,25 @@ void layer_norm_bwd_fused(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
                           at::Tensor mean, at::Tensor rstd,
                           c10::optional<at::Tensor> dadd,
                           c10::optional<at::Tensor> colsum_out) {
-  const bool bf16 = is_bf16(x);
-  const int64_t cols = x.size(-1);
-  const int64_t rows = x.numel() / cols;
-  TORCH_CHECK(!bf16 || cols % 8 == 0, "bf16 LayerNorm needs cols % 8 == 0");
-  TORCH_CHECK((size_t)cols * 2 * sizeof(float) <= 128 * 1024,
-              "LayerNorm backward supports cols <= 16384");
-  check(dgamma, at::kFloat, "dgamma");
-  check(dbeta, at::kFloat, "dbeta");
-  TORCH_CHECK(dx.numel() == x.numel() && dy.numel() == x.numel());
-  TORCH_CHECK(dgamma.numel() == cols && dbeta.numel() == cols);
-  const bool fast = bf16 && cols % 8 == 0 && cols <= 2048;
-  const bool fused = dadd.has_value() || colsum_out.has_value();
-  TORCH_CHECK(fast || !fused,
-              "layer_norm_bwd_fused: dadd/colsum_out need the bf16 fast "
-              "path (cols % 8 == 0, cols <= 2048)");
-  const void* dadd_p = nullptr;
-  float* cs_out = nullptr;
-  if (dadd.has_value()) {
-    check(*dadd, x.scalar_type(), "dadd");
-    TORCH_CHECK(dadd->numel() == x.numel(), "dadd shape mismatch");
-    dadd_p = dadd->data_ptr();
-  }
-  if (colsum_out.has_value()) {
-    check(*colsum_out, at::kFloat, "colsum_out");
-    TORCH_CHECK(colsum_out->numel() == cols, "colsum_out shape mismatch");
-    cs_out = colsum_out->data_ptr<float>();
-  }
-  float* dgp = nullptr;
-  float* dbp = nullptr;
-  float* csp = nullptr;
-  at::Tensor ws;
-  int64_t nparts = 0;
-  if (fast) {
-    const int64_t wave_rows = (rows + 3) / 4;
-    nparts = (wave_rows < 1024 ? wave_rows : 1024) * 4;
-    ws = at::empty({cs_out ? 3 : 2, nparts, cols}, dgamma.options());
-    dgp = ws.data_ptr<float>();
-    dbp = dgp + nparts * cols;
-    if (cs_out) csp = dbp + nparts * cols;
-  }
-  epl_layer_norm_bwd_fused(dx.data_ptr(), dgamma.data_ptr<float>(),
-                           dbeta.data_ptr<float>(), cs_out, dy.data_ptr(),
-                           x.data_ptr(), gamma.data_ptr(), dadd_p,
-                           mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                           dgp, dbp, csp, nparts, rows, cols, bf16,
-                           cur_stream());
+  c10::optional<at::Tensor> no_dy2;
+  ln_bwd_fused_impl(dx, dgamma, dbeta, dy, x, gamma, mean, rstd, dadd,
+                    colsum_out, no_dy2, true, "layer_norm_bwd_fused");
+}
+
+// The bf16 fast path alone, with
+//   dy2        [rows, cols] bf16: a second upstream gradient, dy + dy2 is
+//              formed in fp32 inside the kernel;
+//   dgamma, dbeta, colsum_out: bf16 or fp32, each WRITTEN in its own dtype
+//              (one rounding of the fp32 sum) — no zero fill before, no
+//              cast after, and the same bits on every call.
+void layer_norm_bwd_typed(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
+                          at::Tensor dy, at::Tensor x, at::Tensor gamma,
+                          at::Tensor mean, at::Tensor rstd,
+                          c10::optional<at::Tensor> dadd,
+                          c10::optional<at::Tensor> colsum_out,
+                          c10::optional<at::Tensor> dy2) {
+  ln_bwd_fused_impl(dx, dgamma, dbeta, dy, x, gamma, mean, rstd, dadd,
+                    colsum_out, dy2, false, "layer_norm_bwd_typed");
 }
 
 void bias_gelu_fwd(at::Tensor out, at::Tensor x, at::Tensor bias) {
@@ -316,34 +380,58 @@ void bias_gelu_fwd(at::Tensor out, at::Tensor x, at::Tensor bias) {
                     bf16, cur_stream());
 }
 
-void bias_gelu_bwd(at::Tensor dx, at::Tensor dbias, at::Tensor dy,
-                   at::Tensor x, at::Tensor bias) {
+void bias_gelu_bwd_impl(at::Tensor& dx, at::Tensor& dbias, at::Tensor& dy,
+                        at::Tensor& x, at::Tensor& bias, bool accumulate) {
   const bool bf16 = is_bf16(x);
   const int64_t cols = x.size(-1);
   const int64_t rows = x.numel() / cols;
   TORCH_CHECK(!bf16 || cols % 8 == 0, "bf16 bias_gelu needs cols % 8 == 0");
   TORCH_CHECK((size_t)cols * sizeof(float) <= 128 * 1024,
               "bias_gelu backward supports cols <= 32768");
-  check(dbias, at::kFloat, "dbias");
+  const bool fast = bf16 && cols % 512 == 0;
+  int mode = kAccF32;
+  if (accumulate) {
+    check(dbias, at::kFloat, "dbias");
+  } else {
+    TORCH_CHECK(fast, "bias_gelu_bwd_typed needs the bf16 fast path "
+                      "(cols % 512 == 0)");
+    mode = store_mode(dbias, "dbias");
+  }
+  check(dx, x.scalar_type(), "dx");
+  check(dy, x.scalar_type(), "dy");
+  check(x, x.scalar_type(), "x");
+  check(bias, x.scalar_type(), "bias");
+  TORCH_CHECK(dx.numel() == x.numel() && dy.numel() == x.numel());
+  TORCH_CHECK(dbias.numel() == cols && bias.numel() == cols);
   float* dbp = nullptr;
-  int64_t nwaves = 0;
   at::Tensor ws;
-  if (bf16 && cols % 512 == 0) {
-    const int64_t segs = cols / 512;
-    int64_t per_seg = rows < 1024 ? rows : 1024;
-    per_seg = (per_seg + 3) / 4 * 4;   // keep nwaves % (4*segs) clean
-    nwaves = segs * per_seg;
-    ws = at::empty({nwaves, 512}, dbias.options());
+  if (fast) {
+    ws = at::empty({epl_bias_gelu_bwd_parts(rows), cols},
+                   x.options().dtype(at::kFloat));
     dbp = ws.data_ptr<float>();
   }
-  epl_bias_gelu_bwd(dx.data_ptr(), dbias.data_ptr<float>(), dy.data_ptr(),
-                    x.data_ptr(), bias.data_ptr(), dbp, nwaves, rows, cols,
-                    bf16, cur_stream());
+  epl_bias_gelu_bwd(dx.data_ptr(), dbias.data_ptr(), mode, dy.data_ptr(),
+                    x.data_ptr(), bias.data_ptr(), dbp, rows, cols, bf16,
+                    cur_stream());
+}
+
+// dbias: fp32, zero-initialised by the caller
+void bias_gelu_bwd(at::Tensor dx, at::Tensor dbias, at::Tensor dy,
+                   at::Tensor x, at::Tensor bias) {
+  bias_gelu_bwd_impl(dx, dbias, dy, x, bias, true);
+}
+
+// bf16 fast path alone: dbias (bf16 or fp32) is written in its own dtype,
+// no zero fill before and no cast after
+void bias_gelu_bwd_typed(at::Tensor dx, at::Tensor dbias, at::Tensor dy,
+                         at::Tensor x, at::Tensor bias) {
+  bias_gelu_bwd_impl(dx, dbias, dy, x, bias, false);
 }
 
 void ce_rowstats(at::Tensor logits, at::Tensor targets, at::Tensor row_max,
                  at::Tensor row_sumexp, at::Tensor target_logit,
-                 int64_t vocab_begin, int64_t ignore_index) {
+                 int64_t vocab_begin, int64_t ignore_index,
+                 bool skip_ignored) {
   const bool bf16 = is_bf16(logits);
   const int64_t cols = logits.size(-1);
   const int64_t rows = logits.numel() / cols;
@@ -351,7 +439,7 @@ void ce_rowstats(at::Tensor logits, at::Tensor targets, at::Tensor row_max,
   epl_ce_rowstats(logits.data_ptr(), targets.data_ptr<int64_t>(),
                   row_max.data_ptr<float>(), row_sumexp.data_ptr<float>(),
                   target_logit.data_ptr<float>(), rows, cols, vocab_begin,
-                  ignore_index, bf16, cur_stream());
+                  ignore_index, skip_ignored, bf16, cur_stream());
 }
 
 void ce_backward(at::Tensor dlogits, at::Tensor logits, at::Tensor targets,
@@ -909,9 +997,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dgamma"), py::arg("dbeta"), py::arg("dy"), py::arg("x"),
         py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("dadd") = py::none(), py::arg("colsum_out") = py::none());
+  m.def("layer_norm_bwd_typed", &layer_norm_bwd_typed, py::arg("dx"),
+        py::arg("dgamma"), py::arg("dbeta"), py::arg("dy"), py::arg("x"),
+        py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
+        py::arg("dadd") = py::none(), py::arg("colsum_out") = py::none(),
+        py::arg("dy2") = py::none());
   m.def("bias_gelu_fwd", &bias_gelu_fwd);
   m.def("bias_gelu_bwd", &bias_gelu_bwd);
-  m.def("ce_rowstats", &ce_rowstats);
+  m.def("bias_gelu_bwd_typed", &bias_gelu_bwd_typed);
+  m.def("ce_rowstats", &ce_rowstats, py::arg("logits"), py::arg("targets"),
+        py::arg("row_max"), py::arg("row_sumexp"), py::arg("target_logit"),
+        py::arg("vocab_begin"), py::arg("ignore_index"),
+        py::arg("skip_ignored") = false);
   m.def("ce_backward", &ce_backward);
   m.def("scale_", &scale_);
   m.def("f32_to_bf16", &f32_to_bf16);

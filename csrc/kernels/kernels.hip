@@ -414,40 +414,51 @@ __global__ void layer_norm_fwd_kernel(
   }
 }
 
-// bf16 fast backward: ONE ROW PER WAVE — no barriers at all.  Each wave
-// reduces its row with shuffles, keeps the row image in registers between
+// bf16 fast backward: ONE ROW PER WAVE — no barrier in the row loop.  Each
+// wave reduces its row with shuffles, keeps the row image in registers between
 // the reduction and the dx pass (HBM read-once/write-once; CHUNKS=4
 // re-reads the row from L2 instead), accumulates dgamma/dbeta in
-// registers across its rows and writes them once as one partial row per
-// wave — no atomics here; ln_bwd_partial_reduce_kernel sums the partial
-// rows.  CHUNKS = ceil(cols/8/64), cols <= 2048.
+// registers across its rows.  After the row loop the block's four waves
+// fold their accumulators through LDS in wave order and the block writes
+// ONE partial row per plane — no atomics here; partial_rows_reduce_kernel
+// sums the partial rows in a fixed order.  CHUNKS = ceil(cols/8/64),
+// cols <= 2048.
 //   DADD   : dx += dadd (bf16 [rows, cols]) in fp32 before the single
 //            bf16 rounding — the gradient arriving through the summed
 //            stream of a fused-residual LN.
 //   COLSUM : a third accumulator, the column sum of the fp32 value that
 //            is rounded into dx (DADD included), written to cs_part —
 //            the bias gradient of the Linear that produced x.
-// With both flags off the instruction stream is the two-plane kernel's.
+//   DY2    : a second upstream gradient (bf16 [rows, cols]): dy = dy + dy2
+//            in fp32 right after the loads, never rounded to bf16 — the
+//            two consumers of a post-LN output, without autograd's add
+//            kernel in between.
+// With all flags off the row loop is the two-plane kernel's.
 // The waves-per-SIMD bound pins each CHUNKS to the occupancy its plain
 // form reaches (5 / 3 / 3); to fit the extra plane under it the fused
 // forms stop holding gamma as fp32 registers where those are short:
 // CHUNKS=1 keeps it packed bf16 (4 VGPRs, unpacked at each use), CHUNKS=4
-// stages it once per block in LDS (4 KB).
-template <int CHUNKS, bool CACHE, bool DADD, bool COLSUM>
+// (there also the plain form with DY2) stages it once per block in LDS
+// (4 KB).
+template <int CHUNKS, bool CACHE, bool DADD, bool COLSUM, bool DY2>
 __global__ __launch_bounds__(256, CHUNKS == 1 ? 5 : 3) void
 layer_norm_bwd_bf16_kernel(
     void* __restrict__ dx, float* __restrict__ dg_part,
     float* __restrict__ db_part, float* __restrict__ cs_part,
-    const void* __restrict__ dy, const void* __restrict__ x,
+    const void* __restrict__ dy, const void* __restrict__ dy2,
+    const void* __restrict__ x,
     const void* __restrict__ gamma, const void* __restrict__ dadd,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
     int64_t rows, int64_t cols) {
   using T = unsigned short;
   const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;               // wave in block (0..3)
+  // wave in block (0..3), as a scalar: the row, its base offset and its
+  // mean / rstd then live in SGPRs and the loads address scalar base +
+  // lane offset
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wpb = blockDim.x >> 6;                // waves per block
   constexpr bool FUSED = DADD || COLSUM;
-  constexpr bool G_LDS = FUSED && CHUNKS == 4;    // gamma from LDS
+  constexpr bool G_LDS = (FUSED || DY2) && CHUNKS == 4;  // gamma from LDS
   constexpr bool G_PK = FUSED && CHUNKS == 1;     // gamma packed in VGPRs
   constexpr bool G_F32 = !G_LDS && !G_PK;
   __shared__ __attribute__((aligned(16))) T g_lds[G_LDS ? CHUNKS * 512 : 8];
@@ -503,6 +514,12 @@ layer_norm_bwd_bf16_kernel(
       const int64_t c = ((int64_t)lane + k * 64) * 8;
       if (c >= cols) continue;
       float8 d = load_bf16x8(reinterpret_cast<const T*>(dy) + base + c);
+      if (DY2) {
+        const float8 d2 =
+            load_bf16x8(reinterpret_cast<const T*>(dy2) + base + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d.v[j] += d2.v[j];
+      }
       float8 f = load_bf16x8(reinterpret_cast<const T*>(x) + base + c);
       const float8 g = gamma_at(k, c);
 #pragma unroll
@@ -536,6 +553,12 @@ layer_norm_bwd_bf16_kernel(
       } else {
         // rows in flight fit L2: the re-reads hit cache
         float8 d = load_bf16x8(reinterpret_cast<const T*>(dy) + base + c);
+        if (DY2) {
+          const float8 d2 =
+              load_bf16x8(reinterpret_cast<const T*>(dy2) + base + c);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) d.v[j] += d2.v[j];
+        }
         float8 f = load_bf16x8(reinterpret_cast<const T*>(x) + base + c);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -565,40 +588,120 @@ layer_norm_bwd_bf16_kernel(
       store_bf16x8(reinterpret_cast<T*>(dx) + base + c, o);
     }
   }
-  // one partial row per wave — no atomics, a tiny second kernel reduces
-  const int64_t prow = ((int64_t)blockIdx.x * wpb + wid) * cols;
+  // Fold the block's four waves, outside the row loop: waves 1..3 post
+  // their accumulators to LDS, wave 0 adds them in wave order and writes
+  // the block's partial row (zeros from a wave that owned no row).
+  // CHUNKS <= 2 posts every plane at once (one barrier; 36 KB at most, so
+  // the blocks of a CU still fit their waves-per-SIMD bound in 160 KB);
+  // CHUNKS = 4 posts a plane at a time through one 24 KB buffer.
+  constexpr int PLANES = COLSUM ? 3 : 2;
+  constexpr int GROUP = CHUNKS <= 2 ? PLANES : 1;   // planes per barrier
+  __shared__ __attribute__((aligned(16))) float red[3][GROUP][CHUNKS * 512];
+  const int64_t prow = (int64_t)blockIdx.x * cols;
+  auto post = [&](const float8 (&acc)[CHUNKS], int slot) {
+    if (wid == 0) return;
 #pragma unroll
-  for (int k = 0; k < CHUNKS; ++k) {
-    const int64_t c = ((int64_t)lane + k * 64) * 8;
-    if (c >= cols) continue;
-    store_f32x8(dg_part + prow + c, acc_dg[k]);
-    store_f32x8(db_part + prow + c, acc_db[k]);
-    if (COLSUM) store_f32x8(cs_part + prow + c, acc_cs[k]);
+    for (int k = 0; k < CHUNKS; ++k) {
+      const int c = (lane + k * 64) * 8;
+      if (c < cols) store_f32x8(&red[wid - 1][slot][c], acc[k]);
+    }
+  };
+  auto fold = [&](float8 (&acc)[CHUNKS], int slot, float* part) {
+    if (wid != 0) return;
+#pragma unroll
+    for (int k = 0; k < CHUNKS; ++k) {
+      const int c = (lane + k * 64) * 8;
+      if (c >= cols) continue;
+      for (int w = 0; w < 3; ++w) {
+        const float8 o = load_f32x8(&red[w][slot][c]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[k].v[j] += o.v[j];
+      }
+      store_f32x8(part + prow + c, acc[k]);
+    }
+  };
+  if constexpr (GROUP > 1) {
+    post(acc_dg, 0);
+    post(acc_db, 1);
+    if constexpr (COLSUM) post(acc_cs, GROUP - 1);
+    __syncthreads();
+    fold(acc_dg, 0, dg_part);
+    fold(acc_db, 1, db_part);
+    if constexpr (COLSUM) fold(acc_cs, GROUP - 1, cs_part);
+  } else {
+    post(acc_dg, 0);
+    __syncthreads();
+    fold(acc_dg, 0, dg_part);
+    __syncthreads();
+    post(acc_db, 0);
+    __syncthreads();
+    fold(acc_db, 0, db_part);
+    if constexpr (COLSUM) {
+      __syncthreads();
+      post(acc_cs, 0);
+      __syncthreads();
+      fold(acc_cs, 0, cs_part);
+    }
   }
 }
 
-// reduce the [nparts, cols] partial buffers into dgamma/dbeta (and, with
-// COLSUM, the third plane into colsum).
-// grid = (col_chunks, PSPLIT): each block sums a strided slice of the
-// partial rows for its 256-column range (coalesced row-major reads) and
-// contributes one atomicAdd per column (PSPLIT per column total).
-template <bool COLSUM>
-__global__ void ln_bwd_partial_reduce_kernel(
-    float* __restrict__ dgamma, float* __restrict__ dbeta,
-    float* __restrict__ colsum, const float* __restrict__ dg_part,
-    const float* __restrict__ db_part, const float* __restrict__ cs_part,
-    int64_t nparts, int64_t cols) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  float sg = 0.f, sb = 0.f, sc = 0.f;
-  for (int64_t p = blockIdx.y; p < nparts; p += gridDim.y) {
-    sg += dg_part[p * cols + c];
-    sb += db_part[p * cols + c];
-    if (COLSUM) sc += cs_part[p * cols + c];
+// How the reducers below leave a column's sum: added to the fp32 value
+// that is there (the pre-zeroed outputs of the older bindings), or stored
+// as fp32 / as bf16 (one packed-convert rounding) over whatever was there.
+enum : int { kRedAccF32 = 0, kRedStoreF32 = 1, kRedStoreBF16 = 2 };
+
+struct RedPlane {
+  void* out;            // [cols]
+  const float* part;    // [nparts, cols]
+  int mode;
+};
+struct RedPlanes {
+  RedPlane p[3];
+};
+
+// out[c] (op)= sum of the partial rows of column c, in a fixed order and
+// by one writer: blockIdx.y picks the plane, a block of 1024 threads covers
+// 16 columns (64-byte row segments) with 64 slices of the partial rows.  A
+// thread sums its slice in row order, 16 loads in flight at a time (at
+// 1024 partial rows every load of the kernel is issued before the first
+// add: the kernel is latency bound, not bandwidth bound), then the 64
+// slice sums are added in slice order.  No float atomics; two calls give
+// the same bits.
+constexpr int kRedCols = 16, kRedSlices = 64, kRedDepth = 16;
+
+__global__ __launch_bounds__(kRedCols * kRedSlices) void
+partial_rows_reduce_kernel(RedPlanes planes, int64_t nparts, int64_t cols) {
+  __shared__ float lds[kRedSlices][kRedCols];
+  const RedPlane pl = planes.p[blockIdx.y];
+  const int cx = threadIdx.x % kRedCols;
+  const int sy = threadIdx.x / kRedCols;
+  const int64_t c = (int64_t)blockIdx.x * kRedCols + cx;
+  float sum = 0.f;
+  if (c < cols) {
+    for (int64_t p0 = sy; p0 < nparts; p0 += kRedSlices * kRedDepth) {
+      float v[kRedDepth];
+#pragma unroll
+      for (int i = 0; i < kRedDepth; ++i) {
+        const int64_t p = p0 + (int64_t)i * kRedSlices;
+        v[i] = p < nparts ? pl.part[p * cols + c] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < kRedDepth; ++i) sum += v[i];
+    }
   }
-  atomicAdd(&dgamma[c], sg);
-  atomicAdd(&dbeta[c], sb);
-  if (COLSUM) atomicAdd(&colsum[c], sc);
+  lds[sy][cx] = sum;
+  __syncthreads();
+  if (sy == 0 && c < cols) {
+    float t = lds[0][cx];
+#pragma unroll
+    for (int i = 1; i < kRedSlices; ++i) t += lds[i][cx];
+    if (pl.mode == kRedStoreBF16)
+      reinterpret_cast<unsigned short*>(pl.out)[c] = f2bf(t);
+    else if (pl.mode == kRedStoreF32)
+      reinterpret_cast<float*>(pl.out)[c] = t;
+    else
+      reinterpret_cast<float*>(pl.out)[c] += t;
+  }
 }
 
 // generic (fp32 / large-cols) backward: LDS partials + global re-read
@@ -759,10 +862,12 @@ __global__ void bias_gelu_fwd_kernel(void* __restrict__ out,
 }
 
 // bf16 fast path: one row-segment per wave, dbias accumulated in
-// registers across rows and flushed to per-wave partial rows (the LN
-// partial-reduce kernel pattern).  SEGS = row segments of 512 columns;
-// each wave owns one 512-col segment across ALL rows so its dbias
-// registers cover exactly its columns.
+// registers across rows and flushed to per-wave partial rows.  SEGS = row
+// segments of 512 columns; each wave owns one 512-col segment across ALL
+// rows so its dbias registers cover exactly its columns.  Wave w owns
+// segment w % segs and writes partial row w of [nwaves][512], which is
+// row w / segs of a row-major [nwaves / segs, cols] matrix: the layout
+// partial_rows_reduce_kernel sums, in a fixed order and without atomics.
 __global__ void bias_gelu_bwd_bf16_kernel(
     void* __restrict__ dx, float* __restrict__ db_part,
     const void* __restrict__ dy, const void* __restrict__ x,
@@ -772,7 +877,6 @@ __global__ void bias_gelu_bwd_bf16_kernel(
   const int wid = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int64_t segs = cols / 512;              // cols % 512 == 0
-  const int64_t total = rows * segs;
   float8 acc;
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc.v[j] = 0.f;
@@ -781,8 +885,9 @@ __global__ void bias_gelu_bwd_bf16_kernel(
   // walk (row, my fixed segment) pairs: wave w owns segment w % segs
   const int64_t myseg = wave_id % segs;
   const int64_t c0 = myseg * 512 + (int64_t)lane * 8;
+  const int64_t step = nwaves / segs;
   float8 bw = load_bf16x8(reinterpret_cast<const T*>(bias) + c0);
-  for (int64_t row = wave_id / segs; row < rows; row += nwaves / segs) {
+  for (int64_t row = wave_id / segs; row < rows; row += step) {
     const int64_t base = row * cols + c0;
     float8 d = load_bf16x8(reinterpret_cast<const T*>(dy) + base);
     float8 f = load_bf16x8(reinterpret_cast<const T*>(x) + base);
@@ -796,27 +901,6 @@ __global__ void bias_gelu_bwd_bf16_kernel(
     store_bf16x8_pk(reinterpret_cast<T*>(dx) + base, o);
   }
   store_f32x8(db_part + wave_id * 512 + (int64_t)lane * 8, acc);
-}
-
-// reduce [nwaves, 512-per-seg...] — reuse ln partial reduce over a
-// [nparts, cols] view is not directly applicable; dbias partials are
-// [nwaves][512] keyed by segment: reduce per (segment, col) over the
-// waves owning that segment.
-__global__ void bias_gelu_db_reduce_kernel(
-    float* __restrict__ dbias, const float* __restrict__ db_part,
-    int64_t nwaves, int64_t segs) {
-  // column c (global) = seg * 512 + off; partial p covers segment
-  // p % segs at its [512] row.
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= segs * 512) return;
-  const int64_t seg = c / 512;
-  const int64_t off = c % 512;
-  float sum = 0.f;
-  for (int64_t p = seg + blockIdx.y * segs; p < nwaves;
-       p += (int64_t)gridDim.y * segs) {
-    sum += db_part[p * 512 + off];
-  }
-  atomicAdd(&dbias[c], sum);
 }
 
 template <bool BF16>
@@ -879,12 +963,24 @@ __global__ void ce_rowstats_kernel(const void* __restrict__ logits,
                                    float* __restrict__ row_sumexp,
                                    float* __restrict__ target_logit,
                                    int64_t rows, int64_t cols,
-                                   int64_t vocab_begin, int64_t ignore_index) {
+                                   int64_t vocab_begin, int64_t ignore_index,
+                                   bool skip_ignored) {
   __shared__ float lds[8];
   using T = unsigned short;
   const bool vec = BF16 && (cols % 8 == 0);
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const int64_t base = row * cols;
+    // skip_ignored: a row the loss ignores is not read (uniform over the
+    // block); it gets the statistics of a neutral row, max 0 and sum 1, so
+    // log(sum) + max = 0 and a cross-shard rescale exp(max - gmax) is 1
+    if (skip_ignored && targets[row] == ignore_index) {
+      if (threadIdx.x == 0) {
+        row_max[row] = 0.f;
+        row_sumexp[row] = 1.f;
+        target_logit[row] = 0.f;
+      }
+      continue;
+    }
     float vmax = -INFINITY;
     if (vec) {
       const T* lr = reinterpret_cast<const T*>(logits) + base;
@@ -955,10 +1051,28 @@ __global__ void ce_backward_kernel(void* __restrict__ dlogits,
   const bool vec = BF16 && (cols % 8 == 0);
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     const int64_t base = row * cols;
+    const int64_t tgt = targets[row];
+    if (tgt == ignore_index) {
+      // a row of +0 without reading its logits or statistics (uniform
+      // over the block): g * 0 would be NaN where those are not finite
+      if (vec) {
+        T* dr = reinterpret_cast<T*>(dlogits) + base;
+        for (int64_t c = threadIdx.x * 8; c < cols;
+             c += (int64_t)blockDim.x * 8)
+          *reinterpret_cast<uint4*>(dr + c) = make_uint4(0u, 0u, 0u, 0u);
+      } else {
+        for (int64_t c = threadIdx.x; c < cols; c += blockDim.x) {
+          if (BF16)
+            reinterpret_cast<T*>(dlogits)[base + c] = 0;
+          else
+            reinterpret_cast<float*>(dlogits)[base + c] = 0.f;
+        }
+      }
+      continue;
+    }
     const float m = gmax[row];
     const float inv_sum = 1.f / gsumexp[row];
-    const int64_t tgt = targets[row];
-    const float dl = (tgt == ignore_index ? 0.f : dloss[row] * scale);
+    const float dl = dloss[row] * scale;
     const int64_t tc = tgt - vocab_begin;
     if (vec) {
       const T* lr = reinterpret_cast<const T*>(logits) + base;
@@ -1117,36 +1231,55 @@ __global__ void colsum_reduce_kernel(void* __restrict__ db,
     reinterpret_cast<float*>(db)[c] = s;
 }
 
-// LN fast backward + partial reduce for one (DADD, COLSUM) combination
-template <bool DADD, bool COLSUM>
-static void ln_bwd_fast_launch(void* dx, float* dgamma, float* dbeta,
-                               float* colsum, const void* dy, const void* x,
-                               const void* gamma, const void* dadd,
-                               const float* mean, const float* rstd,
-                               float* dg_part, float* db_part,
-                               float* cs_part, int64_t rows, int64_t cols,
-                               hipStream_t stream) {
+// blocks of the LN fast backward = partial rows per plane
+inline int64_t ln_bwd_parts(int64_t rows) {
   const int64_t wave_rows = (rows + 3) / 4;
-  const int grid = (int)(wave_rows < 1024 ? wave_rows : 1024);
-  if (cols <= 512)
-    hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<1, true, DADD, COLSUM>),
-                       dim3(grid), dim3(256), 0, stream, dx, dg_part,
-                       db_part, cs_part, dy, x, gamma, dadd, mean, rstd,
-                       rows, cols);
-  else if (cols <= 1024)
-    hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<2, true, DADD, COLSUM>),
-                       dim3(grid), dim3(256), 0, stream, dx, dg_part,
-                       db_part, cs_part, dy, x, gamma, dadd, mean, rstd,
-                       rows, cols);
+  return wave_rows < 1024 ? (wave_rows > 0 ? wave_rows : 1) : 1024;
+}
+
+struct LnBwdArgs {
+  void* dx;
+  RedPlanes outs;        // dgamma, dbeta, colsum with their partial planes
+  const void *dy, *dy2, *x, *gamma, *dadd;
+  const float *mean, *rstd;
+  int64_t rows, cols;
+  hipStream_t stream;
+};
+
+// LN fast backward + fixed-order reduce for one flag combination
+template <bool DADD, bool COLSUM, bool DY2>
+static void ln_bwd_fast_launch(const LnBwdArgs& a) {
+  const int grid = (int)ln_bwd_parts(a.rows);
+  float* dg_part = const_cast<float*>(a.outs.p[0].part);
+  float* db_part = const_cast<float*>(a.outs.p[1].part);
+  float* cs_part = const_cast<float*>(a.outs.p[2].part);
+  if (a.cols <= 512)
+    hipLaunchKernelGGL(
+        (layer_norm_bwd_bf16_kernel<1, true, DADD, COLSUM, DY2>), dim3(grid),
+        dim3(256), 0, a.stream, a.dx, dg_part, db_part, cs_part, a.dy, a.dy2,
+        a.x, a.gamma, a.dadd, a.mean, a.rstd, a.rows, a.cols);
+  else if (a.cols <= 1024)
+    hipLaunchKernelGGL(
+        (layer_norm_bwd_bf16_kernel<2, true, DADD, COLSUM, DY2>), dim3(grid),
+        dim3(256), 0, a.stream, a.dx, dg_part, db_part, cs_part, a.dy, a.dy2,
+        a.x, a.gamma, a.dadd, a.mean, a.rstd, a.rows, a.cols);
   else
-    hipLaunchKernelGGL((layer_norm_bwd_bf16_kernel<4, false, DADD, COLSUM>),
-                       dim3(grid), dim3(256), 0, stream, dx, dg_part,
-                       db_part, cs_part, dy, x, gamma, dadd, mean, rstd,
-                       rows, cols);
-  hipLaunchKernelGGL(ln_bwd_partial_reduce_kernel<COLSUM>,
-                     dim3((unsigned)((cols + 255) / 256), 64), dim3(256), 0,
-                     stream, dgamma, dbeta, colsum, dg_part, db_part,
-                     cs_part, (int64_t)grid * 4, cols);
+    hipLaunchKernelGGL(
+        (layer_norm_bwd_bf16_kernel<4, false, DADD, COLSUM, DY2>), dim3(grid),
+        dim3(256), 0, a.stream, a.dx, dg_part, db_part, cs_part, a.dy, a.dy2,
+        a.x, a.gamma, a.dadd, a.mean, a.rstd, a.rows, a.cols);
+  hipLaunchKernelGGL(partial_rows_reduce_kernel,
+                     dim3((unsigned)((a.cols + kRedCols - 1) / kRedCols),
+                          COLSUM ? 3 : 2),
+                     dim3(kRedCols * kRedSlices), 0, a.stream, a.outs, (int64_t)grid, a.cols);
+}
+
+template <bool DADD, bool COLSUM>
+static void ln_bwd_fast_dy2(const LnBwdArgs& a) {
+  if (a.dy2 != nullptr)
+    ln_bwd_fast_launch<DADD, COLSUM, true>(a);
+  else
+    ln_bwd_fast_launch<DADD, COLSUM, false>(a);
 }
 
 // extern "C" launchers (raw pointers + stream; bound to torch in bindings.hip)
@@ -1270,58 +1403,64 @@ void epl_layer_norm_fwd(void* out, const void* x, const void* res,
   }
 }
 
-// dadd / colsum (with its cs_part plane) are optional and only valid on
-// the bf16 fast path (cols % 8 == 0, cols <= 2048); the caller checks.
-void epl_layer_norm_bwd_fused(void* dx, float* dgamma, float* dbeta,
-                              float* colsum, const void* dy, const void* x,
-                              const void* gamma, const void* dadd,
-                              const float* mean, const float* rstd,
-                              float* dg_part, float* db_part,
-                              float* cs_part, int64_t nparts, int64_t rows,
+int64_t epl_layer_norm_bwd_parts(int64_t rows) { return ln_bwd_parts(rows); }
+
+// dadd / dy2 / colsum (with its cs_part plane) are optional and only valid
+// on the bf16 fast path (cols % 8 == 0, cols <= 2048); the caller checks.
+// The partial planes hold epl_layer_norm_bwd_parts(rows) rows of cols
+// floats each.  mode_* (kRedAccF32 / kRedStoreF32 / kRedStoreBF16) say how
+// dgamma, dbeta and colsum are left; the generic path below accumulates
+// into pre-zeroed fp32 and knows no other.
+void epl_layer_norm_bwd_fused(void* dx, void* dgamma, void* dbeta,
+                              void* colsum, int mode_g, int mode_b,
+                              int mode_c, const void* dy, const void* dy2,
+                              const void* x, const void* gamma,
+                              const void* dadd, const float* mean,
+                              const float* rstd, float* dg_part,
+                              float* db_part, float* cs_part, int64_t rows,
                               int64_t cols, bool bf16, hipStream_t stream) {
   if (bf16 && cols % 8 == 0 && cols <= 2048 && dg_part != nullptr) {
     const bool has_cs = colsum != nullptr && cs_part != nullptr;
+    LnBwdArgs a;
+    a.dx = dx;
+    a.outs.p[0] = {dgamma, dg_part, mode_g};
+    a.outs.p[1] = {dbeta, db_part, mode_b};
+    a.outs.p[2] = {has_cs ? colsum : nullptr, has_cs ? cs_part : nullptr,
+                   mode_c};
+    a.dy = dy; a.dy2 = dy2; a.x = x; a.gamma = gamma; a.dadd = dadd;
+    a.mean = mean; a.rstd = rstd;
+    a.rows = rows; a.cols = cols; a.stream = stream;
     if (dadd != nullptr) {
-      if (has_cs)
-        ln_bwd_fast_launch<true, true>(dx, dgamma, dbeta, colsum, dy, x,
-                                       gamma, dadd, mean, rstd, dg_part,
-                                       db_part, cs_part, rows, cols, stream);
-      else
-        ln_bwd_fast_launch<true, false>(dx, dgamma, dbeta, colsum, dy, x,
-                                        gamma, dadd, mean, rstd, dg_part,
-                                        db_part, cs_part, rows, cols, stream);
+      if (has_cs) ln_bwd_fast_dy2<true, true>(a);
+      else ln_bwd_fast_dy2<true, false>(a);
     } else {
-      if (has_cs)
-        ln_bwd_fast_launch<false, true>(dx, dgamma, dbeta, colsum, dy, x,
-                                        gamma, dadd, mean, rstd, dg_part,
-                                        db_part, cs_part, rows, cols, stream);
-      else
-        ln_bwd_fast_launch<false, false>(dx, dgamma, dbeta, colsum, dy, x,
-                                         gamma, dadd, mean, rstd, dg_part,
-                                         db_part, cs_part, rows, cols,
-                                         stream);
+      if (has_cs) ln_bwd_fast_dy2<false, true>(a);
+      else ln_bwd_fast_dy2<false, false>(a);
     }
     return;
   }
   int grid = (int)(rows < 1024 ? rows : 1024);
   const size_t lds_bytes = (size_t)cols * 2 * sizeof(float);
+  float* dg = reinterpret_cast<float*>(dgamma);
+  float* db = reinterpret_cast<float*>(dbeta);
   if (bf16)
     hipLaunchKernelGGL((layer_norm_bwd_kernel<true>), dim3(grid),
-                       dim3(kBlock), lds_bytes, stream, dx, dgamma, dbeta,
+                       dim3(kBlock), lds_bytes, stream, dx, dg, db,
                        dy, x, gamma, mean, rstd, rows, cols);
   else
     hipLaunchKernelGGL((layer_norm_bwd_kernel<false>), dim3(grid),
-                       dim3(kBlock), lds_bytes, stream, dx, dgamma, dbeta,
+                       dim3(kBlock), lds_bytes, stream, dx, dg, db,
                        dy, x, gamma, mean, rstd, rows, cols);
 }
 
 void epl_layer_norm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy,
                         const void* x, const void* gamma, const float* mean,
                         const float* rstd, float* dg_part, float* db_part,
-                        int64_t nparts, int64_t rows, int64_t cols,
-                        bool bf16, hipStream_t stream) {
-  epl_layer_norm_bwd_fused(dx, dgamma, dbeta, nullptr, dy, x, gamma, nullptr,
-                           mean, rstd, dg_part, db_part, nullptr, nparts,
+                        int64_t rows, int64_t cols, bool bf16,
+                        hipStream_t stream) {
+  epl_layer_norm_bwd_fused(dx, dgamma, dbeta, nullptr, kRedAccF32,
+                           kRedAccF32, kRedAccF32, dy, nullptr, x, gamma,
+                           nullptr, mean, rstd, dg_part, db_part, nullptr,
                            rows, cols, bf16, stream);
 }
 
@@ -1340,45 +1479,61 @@ void epl_bias_gelu_fwd(void* out, const void* x, const void* bias,
                        0, stream, out, x, bias, rows, cols);
 }
 
-void epl_bias_gelu_bwd(void* dx, float* dbias, const void* dy, const void* x,
-                       const void* bias, float* db_part, int64_t nwaves,
+// partial rows per 512-column segment of the bf16 fast backward
+int64_t epl_bias_gelu_bwd_parts(int64_t rows) {
+  int64_t per_seg = rows < 1024 ? (rows > 0 ? rows : 1) : 1024;
+  return (per_seg + 3) / 4 * 4;   // whole blocks for every segment count
+}
+
+// db_part: [epl_bias_gelu_bwd_parts(rows), cols] floats, fast path only
+// (bf16, cols % 512 == 0).  mode: how dbias is left (kRed*); the generic
+// path accumulates into pre-zeroed fp32 and knows no other.
+void epl_bias_gelu_bwd(void* dx, void* dbias, int mode, const void* dy,
+                       const void* x, const void* bias, float* db_part,
                        int64_t rows, int64_t cols, bool bf16,
                        hipStream_t stream) {
   if (bf16 && cols % 512 == 0 && db_part != nullptr) {
-    const int grid = (int)(nwaves / 4);
+    const int64_t segs = cols / 512;
+    const int64_t per_seg = epl_bias_gelu_bwd_parts(rows);
+    const int grid = (int)(segs * per_seg / 4);
     hipLaunchKernelGGL(bias_gelu_bwd_bf16_kernel, dim3(grid), dim3(256), 0,
                        stream, dx, db_part, dy, x, bias, rows, cols);
-    const int64_t segs = cols / 512;
-    hipLaunchKernelGGL(bias_gelu_db_reduce_kernel,
-                       dim3((unsigned)((cols + 255) / 256), 32), dim3(256),
-                       0, stream, dbias, db_part, nwaves, segs);
+    RedPlanes outs;
+    outs.p[0] = {dbias, db_part, mode};
+    outs.p[1] = outs.p[2] = {nullptr, nullptr, mode};
+    hipLaunchKernelGGL(partial_rows_reduce_kernel,
+                       dim3((unsigned)((cols + kRedCols - 1) / kRedCols), 1),
+                       dim3(kRedCols * kRedSlices), 0,
+                       stream, outs, per_seg, cols);
     return;
   }
   int grid = (int)(rows < 1024 ? rows : 1024);
   const size_t lds_bytes = (size_t)cols * sizeof(float);
+  float* db = reinterpret_cast<float*>(dbias);
   if (bf16)
     hipLaunchKernelGGL(bias_gelu_bwd_kernel<true>, dim3(grid), dim3(kBlock),
-                       lds_bytes, stream, dx, dbias, dy, x, bias, rows,
-                       cols);
+                       lds_bytes, stream, dx, db, dy, x, bias, rows, cols);
   else
     hipLaunchKernelGGL(bias_gelu_bwd_kernel<false>, dim3(grid), dim3(kBlock),
-                       lds_bytes, stream, dx, dbias, dy, x, bias, rows,
-                       cols);
+                       lds_bytes, stream, dx, db, dy, x, bias, rows, cols);
 }
 
 void epl_ce_rowstats(const void* logits, const int64_t* targets,
                      float* row_max, float* row_sumexp, float* target_logit,
                      int64_t rows, int64_t cols, int64_t vocab_begin,
-                     int64_t ignore_index, bool bf16, hipStream_t stream) {
+                     int64_t ignore_index, bool skip_ignored, bool bf16,
+                     hipStream_t stream) {
   const int grid = (int)(rows < kMaxGrid ? rows : kMaxGrid);
   if (bf16)
     hipLaunchKernelGGL(ce_rowstats_kernel<true>, dim3(grid), dim3(kBlock), 0,
                        stream, logits, targets, row_max, row_sumexp,
-                       target_logit, rows, cols, vocab_begin, ignore_index);
+                       target_logit, rows, cols, vocab_begin, ignore_index,
+                       skip_ignored);
   else
     hipLaunchKernelGGL(ce_rowstats_kernel<false>, dim3(grid), dim3(kBlock), 0,
                        stream, logits, targets, row_max, row_sumexp,
-                       target_logit, rows, cols, vocab_begin, ignore_index);
+                       target_logit, rows, cols, vocab_begin, ignore_index,
+                       skip_ignored);
 }
 
 void epl_ce_backward(void* dlogits, const void* logits, const int64_t* targets,

@@ -48,9 +48,27 @@ class BertCore(nn.Module):
     def forward(self, ids, seqlens=None):
         if seqlens is None and self.pad_token_id is not None:
             seqlens = (ids != self.pad_token_id).sum(1).int()
-        x = self.embeddings(ids)
-        for b in self.blocks:
-            x = b(x) if seqlens is None else b(x, seqlens=seqlens)
+        # Every LayerNorm output on the way has two consumers, the next
+        # attention and the next residual.  Between plain post-LN Blocks
+        # it travels as the pair of FusedLayerNorm.forward_pair (x for the
+        # attention, x_res for the residual), so the LN backward adds the
+        # two gradients itself; a wrapped or replaced block takes and
+        # returns one tensor, used twice, as before.
+        n = len(self.blocks)
+        plain = [type(b) is Block and not b.pre_ln for b in self.blocks]
+        if n and plain[0] and type(self.embeddings) is Embeddings:
+            x, x_res = self.embeddings(ids, pair_out=True)
+        else:
+            x = x_res = self.embeddings(ids)
+        for i, b in enumerate(self.blocks):
+            if plain[i]:
+                # the last block's output has one consumer, the head
+                pair_out = i + 1 < n and plain[i + 1]
+                x = b(x, seqlens=seqlens, x_res=x_res, pair_out=pair_out)
+                x, x_res = x if pair_out else (x, x)
+            else:
+                x = b(x) if seqlens is None else b(x, seqlens=seqlens)
+                x_res = x
         return self.head(x)
 
 

@@ -158,10 +158,24 @@ class Block(nn.Module):
             return mod(x, bias_grad_to_ln=True, **kwargs)
         return mod(x, **kwargs), None
 
-    def forward(self, x, seqlens=None):
+    def forward(self, x, seqlens=None, x_res=None, pair_out=False):
         """seqlens: int32 [B] valid lengths of a right-padded batch; only
-        the attention looks at it (every other op is per token)."""
+        the attention looks at it (every other op is per token).
+
+        x_res / pair_out (post-LN only) carry a LayerNorm output with two
+        consumers across the block boundary as the two tensors of
+        FusedLayerNorm.forward_pair, so the LN backward adds their
+        gradients itself: ``x_res`` is the second copy of the input (the
+        attention takes x, ln1's residual takes x_res; default: x twice),
+        and with ``pair_out`` the block returns both copies of its output
+        for the next block.  A caller that cannot pass the pair on (a
+        pipeline stage boundary, a wrapped block) leaves both out: one
+        tensor is used twice and autograd adds the gradients."""
+        if x_res is None:
+            x_res = x
         if self.pre_ln:
+            if pair_out or x_res is not x:
+                raise ValueError("x_res / pair_out are post-LN only")
             # residual add fused into ln2; the summed stream s is the
             # residual carried forward
             a, pb = self._into_ln(self.attn, SelfAttention, self.ln1(x),
@@ -171,10 +185,12 @@ class Block(nn.Module):
         # post-LN: both residual adds fuse into the LN kernels, and the
         # LN backward returns the bias gradient of the Linear before it
         a, pb = self._into_ln(self.attn, SelfAttention, x, seqlens=seqlens)
-        x = self.ln1(a, residual=x, lin_bias=pb)
-        m, fb = self._into_ln(self.mlp, MLP, x)
-        x = self.ln2(m, residual=x, lin_bias=fb)
-        return x
+        # ln1's output feeds the MLP and ln2's residual
+        h, h_res = self.ln1.forward_pair(a, residual=x_res, lin_bias=pb)
+        m, fb = self._into_ln(self.mlp, MLP, h)
+        if pair_out:
+            return self.ln2.forward_pair(m, residual=h_res, lin_bias=fb)
+        return self.ln2(m, residual=h_res, lin_bias=fb)
 
 
 class Embeddings(nn.Module):
@@ -186,10 +202,15 @@ class Embeddings(nn.Module):
         nn.init.normal_(self.tok.weight, std=0.02)
         nn.init.normal_(self.pos.weight, std=0.02)
 
-    def forward(self, ids):
+    def forward(self, ids, pair_out=False):
+        """pair_out: return the output as the two tensors of
+        FusedLayerNorm.forward_pair, for a first block that takes them as
+        (x, x_res)."""
         s = ids.shape[1]
         pos = torch.arange(s, device=ids.device)
         x = self.tok(ids) + self.pos(pos)[None, :, :]
+        if pair_out:
+            return self.ln.forward_pair(x) if self.ln is not None else (x, x)
         if self.ln is not None:
             x = self.ln(x)
         return x

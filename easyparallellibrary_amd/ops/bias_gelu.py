@@ -43,6 +43,15 @@ class _FusedBiasGelu(torch.autograd.Function):
         x, bias = ctx.saved_tensors
         dy = dy.contiguous()
         cols = x.shape[-1]
+        if use_native(x) and x.dtype == torch.bfloat16 and cols % 512 == 0 \
+                and ctx.param_dtype in (torch.bfloat16, torch.float32):
+            # fast path: the fixed-order reduce writes dbias in the
+            # parameter dtype — no zero fill, no cast, no atomics
+            dx = torch.empty_like(x)
+            dbias = torch.empty(cols, dtype=ctx.param_dtype,
+                                device=x.device)
+            native_ext().bias_gelu_bwd_typed(dx, dbias, dy, x, bias)
+            return dx, dbias
         if use_native(x) and x.dtype in (torch.bfloat16, torch.float32) \
                 and cols % 8 == 0:
             dx = torch.empty_like(x)

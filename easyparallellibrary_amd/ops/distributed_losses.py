@@ -28,8 +28,12 @@ class _VocabParallelCE(torch.autograd.Function):
             lmax = torch.empty(rows, dtype=torch.float32, device=dev)
             lsum = torch.empty(rows, dtype=torch.float32, device=dev)
             tlogit = torch.empty(rows, dtype=torch.float32, device=dev)
+            # rows the loss ignores (85 % of an MLM batch) are not read:
+            # they get max 0, sumexp 1, target logit 0.  Every shard sees
+            # the same targets and skips the same rows, the merge below
+            # gives them gsum = 1, and where(valid, ...) discards it.
             ext.ce_rowstats(logits, targets, lmax, lsum, tlogit, vocab_begin,
-                            ignore_index)
+                            ignore_index, skip_ignored=True)
         else:
             lf = logits.float()
             lmax = lf.max(dim=1).values
@@ -77,8 +81,11 @@ class _VocabParallelCE(torch.autograd.Function):
             safe = (targets - ctx.vocab_begin).clamp(0, cols - 1)
             onehot = torch.zeros_like(p)
             onehot[in_range, safe[in_range]] = 1.0
-            mask = (targets != ctx.ignore_index).float()[:, None]
-            dlogits = ((p - onehot) * dloss[:, None] * mask).to(logits.dtype)
+            # a select, not a product with 0: an ignored row's logits may
+            # be non-finite and its gradient is +0 all the same
+            valid = (targets != ctx.ignore_index)[:, None]
+            dlogits = torch.where(valid, (p - onehot) * dloss[:, None],
+                                  torch.zeros_like(p)).to(logits.dtype)
         return dlogits, None, None, None, None
 
 

@@ -8,10 +8,13 @@ the fp32 row image in LDS between the statistics and normalize passes
 (no HBM re-read), and — with a residual input — folds the residual add
 into the same pass, eliminating the separate elementwise-add kernel
 entirely (post-LN BERT: x = LN(x + sublayer(x))).  The backward caches
-xhat / dy in registers, writes dgamma/dbeta as per-wave partial rows
-that a small kernel reduces, and can fold two neighbours in: the
-gradient arriving through the summed stream (dx += ds) and the bias
-gradient of the Linear that produced x (column sum of dx).
+xhat / dy in registers, writes dgamma/dbeta as one partial row per block
+that a small fixed-order kernel reduces and writes in the parameter
+dtype (no zero fill, no cast, no atomics), and can fold three neighbours
+in: the gradient arriving through the summed stream (dx += ds), the bias
+gradient of the Linear that produced x (column sum of dx), and the add of
+the gradients of an output with two consumers (dy + dy2, see
+FusedLayerNorm.forward_pair).
 CPU fallback = identical math in torch (numerics tests compare against a
 plain fp32 torch reference).
 """
@@ -31,6 +34,13 @@ from easyparallellibrary_amd.ops.dispatch import native_ext, use_native
 # bias gradient.  Read once; the A/B and the tests flip it.
 _LN_BWD_FUSE = os.environ.get("EPL_LN_BWD_FUSE", "1") == "1"
 
+# EPL_LN_BWD_FORK: "1" (default) = forward_pair hands a LayerNorm output
+# with two consumers out as two tensors on one storage, so their gradients
+# reach the LN backward separately and the kernel adds them while it
+# loads; "0" = one tensor used twice, autograd adds the gradients in a
+# kernel of its own.  Read once; the A/B and the tests flip it.
+_LN_BWD_FORK = os.environ.get("EPL_LN_BWD_FORK", "1") == "1"
+
 
 def _native_ok(x):
     return (use_native(x) and x.dtype in (torch.bfloat16, torch.float32)
@@ -45,29 +55,46 @@ def _bwd_fast_ok(x):
 
 
 def layer_norm_bwd_fused(dy, x, gamma, mean, rstd, dadd=None,
-                         want_colsum=False):
-    """Native LN backward of ``dy`` at the saved (x, mean, rstd), plus
-    ``dadd`` added into dx and, if asked, colsum = dx.sum(rows) in fp32.
-    Fast-path shapes do both inside the kernel; the others keep the
-    separate add and sum.  Returns (dx, dgamma, dbeta, colsum | None)."""
+                         want_colsum=False, dy2=None, param_dtype=None,
+                         colsum_dtype=None):
+    """Native LN backward of ``dy (+ dy2)`` at the saved (x, mean, rstd),
+    plus ``dadd`` added into dx and, if asked, colsum = dx.sum(rows).
+    Fast-path shapes do all of it inside the kernel and get dgamma / dbeta
+    in ``param_dtype`` and colsum in ``colsum_dtype`` (both default fp32)
+    straight from the reduce kernel; the others keep the separate adds,
+    sum and casts.  Returns (dx, dgamma, dbeta, colsum | None)."""
     cols = x.shape[-1]
+    param_dtype = param_dtype or torch.float32
+    colsum_dtype = colsum_dtype or torch.float32
     dx = torch.empty_like(x)
-    dgamma = torch.zeros(cols, dtype=torch.float32, device=x.device)
-    dbeta = torch.zeros(cols, dtype=torch.float32, device=x.device)
     if _bwd_fast_ok(x):
-        colsum = (torch.zeros(cols, dtype=torch.float32, device=x.device)
+        typed = (torch.bfloat16, torch.float32)
+        # the reduce kernel writes bf16 or fp32; anything else is cast
+        pd = param_dtype if param_dtype in typed else torch.float32
+        cd = colsum_dtype if colsum_dtype in typed else torch.float32
+        dgamma = torch.empty(cols, dtype=pd, device=x.device)
+        dbeta = torch.empty(cols, dtype=pd, device=x.device)
+        colsum = (torch.empty(cols, dtype=cd, device=x.device)
                   if want_colsum else None)
         if dadd is not None:
             dadd = dadd.contiguous().to(x.dtype)
-        native_ext().layer_norm_bwd_fused(dx, dgamma, dbeta, dy, x, gamma,
-                                          mean, rstd, dadd, colsum)
-        return dx, dgamma, dbeta, colsum
+        if dy2 is not None:
+            dy2 = dy2.contiguous().to(x.dtype)
+        native_ext().layer_norm_bwd_typed(dx, dgamma, dbeta, dy, x, gamma,
+                                          mean, rstd, dadd, colsum, dy2)
+        if colsum is not None:
+            colsum = colsum.to(colsum_dtype)
+        return (dx, dgamma.to(param_dtype), dbeta.to(param_dtype), colsum)
+    if dy2 is not None:
+        dy = dy + dy2
+    dgamma = torch.zeros(cols, dtype=torch.float32, device=x.device)
+    dbeta = torch.zeros(cols, dtype=torch.float32, device=x.device)
     native_ext().layer_norm_bwd(dx, dgamma, dbeta, dy, x, gamma, mean, rstd)
     if dadd is not None:
         dx = dx + dadd
     colsum = (dx.reshape(-1, cols).sum(dim=0, dtype=torch.float32)
-              if want_colsum else None)
-    return dx, dgamma, dbeta, colsum
+              .to(colsum_dtype) if want_colsum else None)
+    return dx, dgamma.to(param_dtype), dbeta.to(param_dtype), colsum
 
 
 class _FusedLayerNorm(torch.autograd.Function):
@@ -77,10 +104,15 @@ class _FusedLayerNorm(torch.autograd.Function):
     ``lin_bias`` (optional) is the bias parameter of the Linear that
     produced x, whose forward ran with that bias detached.  It does not
     enter the forward math; its gradient is the column sum of dx, which
-    the backward kernel accumulates next to dgamma/dbeta."""
+    the backward kernel accumulates next to dgamma/dbeta.
+
+    ``fork``: return y twice, as two tensors on one storage (y, y2[, s]),
+    for a y with two consumers: backward then receives the two gradients
+    separately and the kernel adds them in fp32 as it loads them."""
 
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps, lin_bias=None):
+    def forward(ctx, x, residual, gamma, beta, eps, lin_bias=None,
+                fork=False):
         x = x.contiguous()
         cols = x.shape[-1]
         rows = x.numel() // cols
@@ -119,13 +151,21 @@ class _FusedLayerNorm(torch.autograd.Function):
             # an unused output (post-LN drops s) must not cost a zero
             # fill and an add of zeros in backward
             ctx.set_materialize_grads(False)
+        ctx.fork = fork
+        outs = (out, out.view_as(out)) if fork else (out,)
         if has_res:
-            return out, s
-        return out
+            outs = outs + (s,)
+        return outs if len(outs) > 1 else out
 
     @staticmethod
     def backward(ctx, dy, *rest):
         norm_in, gamma, mean, rstd = ctx.saved_tensors
+        dy2 = None
+        if ctx.fork:
+            # the second copy's gradient; an unused copy arrives as None
+            dy2, rest = rest[0], rest[1:]
+            if dy is None:
+                dy, dy2 = dy2, None
         # with residual, grad also flows through the returned sum s
         ds = rest[0] if (ctx.has_res and rest) else None
         # switch off: the summed stream's gradient is added separately
@@ -145,8 +185,12 @@ class _FusedLayerNorm(torch.autograd.Function):
         elif _native_ok(norm_in):
             dx, dgamma, dbeta, colsum = layer_norm_bwd_fused(
                 dy.contiguous(), norm_in, gamma.contiguous(), mean, rstd,
-                dadd=ds, want_colsum=want_db)
+                dadd=ds, want_colsum=want_db, dy2=dy2,
+                param_dtype=ctx.param_dtype, colsum_dtype=ctx.bias_dtype)
         else:
+            if dy2 is not None:
+                # in the compute dtype, as autograd's own add
+                dy = dy + dy2
             xf = norm_in.float().reshape(rows, cols)
             dyf = dy.float().reshape(rows, cols)
             xhat = (xf - mean[:, None]) * rstd[:, None]
@@ -169,7 +213,8 @@ class _FusedLayerNorm(torch.autograd.Function):
             dx = dx + ds_late
         dbias = colsum.to(ctx.bias_dtype) if colsum is not None else None
         # d(x) == d(residual) — the add distributes the gradient
-        return (dx, dx if ctx.has_res else None, dgamma, dbeta, None, dbias)
+        return (dx, dx if ctx.has_res else None, dgamma, dbeta, None, dbias,
+                None)
 
 
 class FusedLayerNorm(nn.Module):
@@ -193,6 +238,19 @@ class FusedLayerNorm(nn.Module):
         out, _ = _FusedLayerNorm.apply(x, residual, self.weight, self.bias,
                                        self.eps, lin_bias)
         return out
+
+    def forward_pair(self, x, residual=None, lin_bias=None):
+        """forward() for an output with TWO consumers: returns (y, y2),
+        the same values twice.  With the fork on (EPL_LN_BWD_FORK, and
+        grad mode) they are two tensors on one storage and each consumer
+        takes its own, so the LN backward kernel receives both gradients
+        and adds them itself; otherwise y2 is y and autograd adds."""
+        if not (_LN_BWD_FORK and torch.is_grad_enabled()):
+            y = self.forward(x, residual=residual, lin_bias=lin_bias)
+            return y, y
+        outs = _FusedLayerNorm.apply(x, residual, self.weight, self.bias,
+                                     self.eps, lin_bias, True)
+        return outs[0], outs[1]
 
     def forward_with_sum(self, x, residual, lin_bias=None):
         """(ln(x+residual), x+residual) — pre-LN blocks keep the sum as
