@@ -39,10 +39,8 @@
 // (ds_read_b128) for S and dP and by columns (ds_read_b64_tr_b16) for
 // dV^T, dK^T and dQ; the dV/dK kernels stage the chunk's -lse/scale and
 // -delta next to it and start the S and dP chains from them.
-// EPL_ATTN_BWD_TILES=legacy selects the previous tile bodies (2-byte
-// LDS gathers, row constants from global memory) for a same-process
-// A/B.  All kernels take (batch, head, seq) strides so the qkv-unbind
-// views are consumed without copies.
+// All kernels take (batch, head, seq) strides so the qkv-unbind views are
+// consumed without copies.
 //
 // Non-causal grids run in the XCD-local block order of
 // attn_block_order.h: the 128-row blocks of a batch-head, which read the
@@ -51,7 +49,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "attn_block_order.h"
@@ -76,24 +73,13 @@ DEVI float bf2f(short u) {
   return v.f;
 }
 
-DEVI unsigned short f2bf(float f) {
-  union { float f; unsigned int i; } v;
-  v.f = f;
-  unsigned int lsb = (v.i >> 16) & 1u;
-  return (unsigned short)((v.i + 0x7fffu + lsb) >> 16);
-}
-
-DEVI unsigned int pack2(float a, float b) {
-  return (unsigned int)f2bf(a) | ((unsigned int)f2bf(b) << 16);
-}
-
 // C/D row for reg r, half hi of v_mfma_f32_32x32x16_bf16
 DEVI int crow(int r, int hi) {
   return (r & 3) + 8 * (r >> 2) + 4 * hi;
 }
 
 // two floats -> packed bf16 pair, round-to-nearest-even, in one
-// v_cvt_pk_bf16_f32 (bit-identical to pack2 for finite values)
+// v_cvt_pk_bf16_f32
 DEVI unsigned int cvt_pk_bf16(float a, float b) {
   f32x2 f = {a, b};
   return __builtin_bit_cast(unsigned int,
@@ -102,14 +88,11 @@ DEVI unsigned int cvt_pk_bf16(float a, float b) {
 
 // assemble the P^T mfma operand from 8 f32 scores (p[0..7] at rows
 // crow(0..7, hi)): returns bf16x8 with element j = P at kv = hi*8+j.
-// HW selects the packed hardware convert; the legacy backward tiles keep
-// the software rounding so the A/B switch compares the parent's bodies.
-template <bool HW = false>
 DEVI bf16x8 assemble_pfrag(const float* p) {
-  unsigned int c0 = HW ? cvt_pk_bf16(p[0], p[1]) : pack2(p[0], p[1]);
-  unsigned int c1 = HW ? cvt_pk_bf16(p[2], p[3]) : pack2(p[2], p[3]);
-  unsigned int c2 = HW ? cvt_pk_bf16(p[4], p[5]) : pack2(p[4], p[5]);
-  unsigned int c3 = HW ? cvt_pk_bf16(p[6], p[7]) : pack2(p[6], p[7]);
+  unsigned int c0 = cvt_pk_bf16(p[0], p[1]);
+  unsigned int c1 = cvt_pk_bf16(p[2], p[3]);
+  unsigned int c2 = cvt_pk_bf16(p[4], p[5]);
+  unsigned int c3 = cvt_pk_bf16(p[6], p[7]);
   i32x2 r = __builtin_amdgcn_permlane32_swap((int)c0, (int)c2, false, false);
   i32x2 s = __builtin_amdgcn_permlane32_swap((int)c1, (int)c3, false, false);
   union { unsigned int d[4]; bf16x8 v; } out;
@@ -121,18 +104,17 @@ DEVI bf16x8 assemble_pfrag(const float* p) {
 }
 
 // dual-use LDS image (row reads + transposed reads) of the backward's
-// new tile bodies and of the forward's V tile: layout and fragment
-// readers in attn_lds_image.h
+// tile bodies and of the forward's V tile: layout and fragment readers in
+// attn_lds_image.h
 using attn_img::img_off;
 using attn_img::img_pitch;
 using attn_img::tr_frag;
 
-// staging-store address of columns col..col+7 (col % 8 == 0) of a row:
-// the legacy tiles' padded rows, or the dual-use image of the new ones
-template <bool TR, int D>
-DEVI short* img_at(short (&img)[64][TR ? img_pitch<D>() : D + 8], int row,
-                   int col) {
-  return TR ? &img[0][0] + img_off<D>(row, col >> 3) : &img[row][col];
+// staging-store address of columns col..col+7 (col % 8 == 0) of a row of
+// the dual-use image
+template <int D>
+DEVI short* img_at(short (&img)[64][img_pitch<D>()], int row, int col) {
+  return &img[0][0] + img_off<D>(row, col >> 3);
 }
 
 // the 16 per-row constants of one lane's accumulator rows
@@ -151,9 +133,10 @@ DEVI f32x16 load_rowconst(const float* c32, int hi) {
   return out;
 }
 
-// MASKED tiles: the legacy test (qg >= seq || (causal && mykv > qg) ||
-// mykv >= seq) for tile row c = crow(r, hi), qg = q0 + c, as two 32-bit
-// bounds: masked <=> c < lo || c >= hi_
+// MASKED tiles: element (qg, mykv) of tile row c = crow(r, hi),
+// qg = q0 + c, is masked under the condition qg >= seq ||
+// (causal && mykv > qg) || mykv >= seq, held as two 32-bit bounds:
+// masked <=> c < lo || c >= hi_
 struct RowMask {
   int lo, hi_;
   DEVI RowMask(int64_t q0, int64_t seq, int64_t mykv, int causal) {
@@ -375,8 +358,8 @@ DEVI void fwd_tile(const short (&ldsK)[64][D + 8], const short* imgV,
     if (hi == 0 && myq < seq)
       maskrow[myq * mask_w + (kvs >> 5)] = wlo | whi;
   }
-  bf16x8 pf0 = assemble_pfrag<true>(&s[0]);
-  bf16x8 pf1 = assemble_pfrag<true>(&s[8]);
+  bf16x8 pf0 = assemble_pfrag(&s[0]);
+  bf16x8 pf1 = assemble_pfrag(&s[8]);
 #pragma unroll
   for (int kc = 0; kc < 2; ++kc) {
     bf16x8 pf = kc == 0 ? pf0 : pf1;
@@ -585,136 +568,22 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(
 // rationale as the forward v3 split).
 // ============================================================================
 
-// one 32-row q sub-tile (of the 64-row staged chunk) of the dV
-// accumulation; `sub` selects the LDS half.  DROP: dV = P_d^T dO, so P
-// is masked+rescaled with the forward's keep bits (bit mykv&31 of the
-// mask word of row qg — one broadcast word load per row).
-template <bool MASKED, bool DROP, int D>
-DEVI void dv_tile(const short (&ldsQ)[64][D + 8],
-                  const short (&ldsDO)[64][D + 8],
-                  int sub, int64_t q0, int64_t seq, int64_t mykv,
-                  float scale, int causal, const float* lsep,
-                  const bf16x8 (&kfrag)[D / 16], f32x16 (&dvt)[D / 32],
-                  int lkv, int hi, const unsigned int* maskrow,
-                  int64_t mask_w, float inv_keep) {
-  f32x16 st = {};
-#pragma unroll
-  for (int c = 0; c < D / 16; ++c) {
-    bf16x8 qf = *reinterpret_cast<const bf16x8*>(
-        &ldsQ[sub + lkv][hi * 8 + 16 * c]);
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfrag[c], st, 0, 0, 0);
-  }
-  float p[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t qg = q0 + crow(r, hi);
-    const int64_t qgc = qg < seq ? qg : seq - 1;
-    if (MASKED) {
-      bool masked = qg >= seq || (causal && mykv > qg) || mykv >= seq;
-      p[r] = masked ? 0.f : __expf(st[r] * scale - lsep[qgc]);
-    } else {
-      p[r] = __expf(st[r] * scale - lsep[qg]);
-    }
-    if (DROP) {
-      const int64_t kvc = mykv < seq ? mykv : seq - 1;
-      const unsigned int w = maskrow[qgc * mask_w + (kvc >> 5)];
-      p[r] *= ((w >> (kvc & 31)) & 1u) ? inv_keep : 0.f;
-    }
-  }
-  bf16x8 pb0 = assemble_pfrag(&p[0]);
-  bf16x8 pb1 = assemble_pfrag(&p[8]);
-#pragma unroll
-  for (int qc = 0; qc < 2; ++qc) {
-    bf16x8 pb = qc == 0 ? pb0 : pb1;
-#pragma unroll
-    for (int dj = 0; dj < D / 32; ++dj) {
-      bf16x8 dot;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int qr = sub + qc * 16 + hi * 8 + j;
-        dot[j] = ldsDO[qr][dj * 32 + lkv];
-      }
-      dvt[dj] =
-          __builtin_amdgcn_mfma_f32_32x32x16_bf16(dot, pb, dvt[dj], 0, 0, 0);
-    }
-  }
-}
-
-// one 32-row q sub-tile of the dK accumulation.  DROP mirrors dq_tile:
-// P undropped, the dO.V term masked+rescaled.
-template <bool MASKED, bool DROP, int D>
-DEVI void dk_tile(const short (&ldsQ)[64][D + 8],
-                  const short (&ldsDO)[64][D + 8],
-                  int sub, int64_t q0, int64_t seq, int64_t mykv,
-                  float scale, int causal, const float* lsep,
-                  const float* dltp, const bf16x8 (&kfrag)[D / 16],
-                  const bf16x8 (&vfrag)[D / 16], f32x16 (&dkt)[D / 32],
-                  int lkv, int hi, const unsigned int* maskrow,
-                  int64_t mask_w, float inv_keep) {
-  f32x16 st = {};
-  f32x16 dpt = {};
-#pragma unroll
-  for (int c = 0; c < D / 16; ++c) {
-    bf16x8 qf = *reinterpret_cast<const bf16x8*>(
-        &ldsQ[sub + lkv][hi * 8 + 16 * c]);
-    bf16x8 dof = *reinterpret_cast<const bf16x8*>(
-        &ldsDO[sub + lkv][hi * 8 + 16 * c]);
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfrag[c], st, 0, 0, 0);
-    dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vfrag[c], dpt, 0, 0,
-                                                  0);
-  }
-  float ds[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t qg = q0 + crow(r, hi);
-    const int64_t qgc = qg < seq ? qg : seq - 1;
-    float dp = dpt[r];
-    if (DROP) {
-      const int64_t kvc = mykv < seq ? mykv : seq - 1;
-      const unsigned int w = maskrow[qgc * mask_w + (kvc >> 5)];
-      dp *= ((w >> (kvc & 31)) & 1u) ? inv_keep : 0.f;
-    }
-    if (MASKED) {
-      bool masked = qg >= seq || (causal && mykv > qg) || mykv >= seq;
-      float pv = masked ? 0.f : __expf(st[r] * scale - lsep[qgc]);
-      ds[r] = masked ? 0.f : pv * (dp - dltp[qgc]) * scale;
-    } else {
-      float pv = __expf(st[r] * scale - lsep[qg]);
-      ds[r] = pv * (dp - dltp[qg]) * scale;
-    }
-  }
-  bf16x8 db0 = assemble_pfrag(&ds[0]);
-  bf16x8 db1 = assemble_pfrag(&ds[8]);
-#pragma unroll
-  for (int qc = 0; qc < 2; ++qc) {
-    bf16x8 db = qc == 0 ? db0 : db1;
-#pragma unroll
-    for (int dj = 0; dj < D / 32; ++dj) {
-      bf16x8 qt;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int qr = sub + qc * 16 + hi * 8 + j;
-        qt[j] = ldsQ[qr][dj * 32 + lkv];
-      }
-      dkt[dj] =
-          __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt, db, dkt[dj], 0, 0, 0);
-    }
-  }
-}
-
 // ----------------------------------------------------------------------------
-// New tile bodies (default; EPL_ATTN_BWD_TILES=legacy selects the ones
-// above).  Same products; what changes is how the operands arrive:
-//  * Q/dO live in the dual-use image (img_off) and the transposed
-//    fragments come from two ds_read_b64_tr_b16 instead of eight 2-byte
-//    reads;
+// Tile bodies: one 32-row q sub-tile (`sub` selects the half of the
+// 64-row staged chunk) of the dV or dK accumulation.
+//  * Q/dO live in the dual-use image (img_off): row fragments by
+//    ds_read_b128, each transposed fragment by two ds_read_b64_tr_b16;
 //  * lse (and delta) of the chunk's 64 rows are staged in LDS with the
-//    chunk and read as four ds_read_b128 instead of 16 global loads;
+//    chunk and read as four ds_read_b128;
 //  * bf16 rounding is v_cvt_pk_bf16_f32.
 // lseL/dltL point at the 32 row constants of this sub-tile, staged as
 // -lse/scale and -delta so the S and dP chains start from them and
 // P = exp2(scale*log2(e) * S') needs no subtraction; rows past seq hold
-// the clamped row's value, as the legacy bodies read it.
+// the clamped row's value.
+// DROP, dV = P_d^T dO: P is masked+rescaled with the forward's keep bits
+// (bit mykv&31 of the mask word of row qg — one broadcast word load per
+// row).  DROP, dK mirrors dq_tile_tr: P undropped, the dO.V term
+// masked+rescaled.
 // ----------------------------------------------------------------------------
 template <bool MASKED, bool DROP, int D>
 DEVI void dv_tile_tr(const short* imgQ, const short* imgDO,
@@ -749,8 +618,8 @@ DEVI void dv_tile_tr(const short* imgQ, const short* imgDO,
       p[r] *= ((w >> (kvc & 31)) & 1u) ? inv_keep : 0.f;
     }
   }
-  bf16x8 pb0 = assemble_pfrag<true>(&p[0]);
-  bf16x8 pb1 = assemble_pfrag<true>(&p[8]);
+  bf16x8 pb0 = assemble_pfrag(&p[0]);
+  bf16x8 pb1 = assemble_pfrag(&p[8]);
   const int lane = hi * 32 + lkv;
 #pragma unroll
   for (int qc = 0; qc < 2; ++qc) {
@@ -808,8 +677,8 @@ DEVI void dk_tile_tr(const short* imgQ, const short* imgDO,
     else
       ds[r] = __builtin_amdgcn_exp2f(st[r] * c2) * dp * scale;
   }
-  bf16x8 db0 = assemble_pfrag<true>(&ds[0]);
-  bf16x8 db1 = assemble_pfrag<true>(&ds[8]);
+  bf16x8 db0 = assemble_pfrag(&ds[0]);
+  bf16x8 db1 = assemble_pfrag(&ds[8]);
   const int lane = hi * 32 + lkv;
 #pragma unroll
   for (int qc = 0; qc < 2; ++qc) {
@@ -823,9 +692,9 @@ DEVI void dk_tile_tr(const short* imgQ, const short* imgDO,
   }
 }
 
-template <bool DROP, bool DBUF, int D, bool TR>
+template <bool DROP, bool DBUF, int D>
 __global__ __launch_bounds__(256, D == 64 ? (DBUF ? 3 : 4)
-                                          : (TR && !DROP ? 3 : 2))
+                                          : (!DROP ? 3 : 2))
 void attn_bwd_dv_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ dout, const float* __restrict__ lse,
@@ -835,8 +704,8 @@ void attn_bwd_dv_kernel(
     int64_t g_sh, int64_t g_ss,
     const unsigned int* __restrict__ mask, int64_t mask_w,
     float inv_keep, const int* __restrict__ seqlens) {
-  // TR: dual-use image + the chunk's 64 -lse/scale values
-  constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
+  // dual-use image + the chunk's 64 -lse/scale values
+  constexpr int PITCH = img_pitch<D>();
   __shared__ __attribute__((aligned(16))) short
       ldsQ[DBUF ? 2 : 1][64][PITCH];
   __shared__ __attribute__((aligned(16))) short
@@ -887,10 +756,10 @@ void attn_bwd_dv_kernel(
   // global loads so they hide under this chunk's compute (the fwd v7
   // staging pattern applied to the q/dO loop).
   bf16x8 rq[2][D / 64], rdo[2][D / 64];
-  float rl = 0.f;   // TR: wave 0 carries the chunk's -lse/scale values
+  float rl = 0.f;   // wave 0 carries the chunk's -lse/scale values
   const float neg_inv_scale = -1.f / scale;
   auto prefetch = [&](int64_t q0) {
-    if (TR && wave == 0) {
+    if (wave == 0) {
       const int64_t qr = q0 + lane;
       rl = lsep[qr < len ? qr : len - 1] * neg_inv_scale;
     }
@@ -908,24 +777,24 @@ void attn_bwd_dv_kernel(
     }
   };
   auto commit = [&](int buf) {
-    if (TR && wave == 0) ldsL[buf][lane] = rl;
+    if (wave == 0) ldsL[buf][lane] = rl;
 #pragma unroll
     for (int half = 0; half < 2; ++half)
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsQ[buf], stage_row + half * 32,
-                          stage_seg + s * 64)) =
+            img_at<D>(ldsQ[buf], stage_row + half * 32,
+                      stage_seg + s * 64)) =
             rq[half][s];
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsDO[buf], stage_row + half * 32,
-                          stage_seg + s * 64)) =
+            img_at<D>(ldsDO[buf], stage_row + half * 32,
+                      stage_seg + s * 64)) =
             rdo[half][s];
       }
   };
   auto stage_q64 = [&](int64_t q0) {
     __syncthreads();
-    if (TR && wave == 0) {
+    if (wave == 0) {
       const int64_t qr = q0 + lane;
       ldsL[0][lane] = lsep[qr < len ? qr : len - 1] * neg_inv_scale;
     }
@@ -936,13 +805,13 @@ void attn_bwd_dv_kernel(
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsQ[0], stage_row + half * 32,
-                          stage_seg + seg)) =
+            img_at<D>(ldsQ[0], stage_row + half * 32,
+                      stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 qp + qr * in_ss + stage_seg + seg);
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsDO[0], stage_row + half * 32,
-                          stage_seg + seg)) =
+            img_at<D>(ldsDO[0], stage_row + half * 32,
+                      stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 dop + qr * do_ss + stage_seg + seg);
       }
@@ -952,18 +821,13 @@ void attn_bwd_dv_kernel(
 
   const unsigned int* maskrow =
       DROP ? mask + bh * seq * mask_w : (const unsigned int*)nullptr;
-  // one 32-row sub-tile from LDS buffer rb: new or legacy body
+  // one 32-row sub-tile from LDS buffer rb
   auto tile = [&](auto masked, int rb, int sub, int64_t q0s) {
     constexpr bool M = decltype(masked)::value;
-    if constexpr (TR)
-      dv_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
-                             &ldsL[rb][sub], sub, q0s, len, mykv, scale,
-                             causal, kfrag, dvt, lkv, hi, maskrow, mask_w,
-                             inv_keep);
-    else
-      dv_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, len, mykv, scale,
-                          causal, lsep, kfrag, dvt, lkv, hi, maskrow,
-                          mask_w, inv_keep);
+    dv_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
+                           &ldsL[rb][sub], sub, q0s, len, mykv, scale,
+                           causal, kfrag, dvt, lkv, hi, maskrow, mask_w,
+                           inv_keep);
   };
   constexpr std::true_type MASKED_T{};
   constexpr std::false_type PLAIN_T{};
@@ -1034,18 +898,11 @@ void attn_bwd_dv_kernel(
   short* dvp = dv + (bh / heads) * g_sb + (bh % heads) * g_sh +
                mykv * g_ss;
 #pragma unroll
-  for (int dj = 0; dj < D / 32; ++dj) {
-    if constexpr (TR) {
-      store_acc_bf16(dvp + dj * 32, dvt[dj], hi);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        dvp[dj * 32 + crow(r, hi)] = (short)f2bf(dvt[dj][r]);
-    }
-  }
+  for (int dj = 0; dj < D / 32; ++dj)
+    store_acc_bf16(dvp + dj * 32, dvt[dj], hi);
 }
 
-template <bool DROP, bool DBUF, int D, bool TR>
+template <bool DROP, bool DBUF, int D>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -1056,12 +913,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     int64_t g_sh, int64_t g_ss,
     const unsigned int* __restrict__ mask, int64_t mask_w,
     float inv_keep, const int* __restrict__ seqlens) {
-  constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
+  constexpr int PITCH = img_pitch<D>();
   __shared__ __attribute__((aligned(16))) short
       ldsQ[DBUF ? 2 : 1][64][PITCH];
   __shared__ __attribute__((aligned(16))) short
       ldsDO[DBUF ? 2 : 1][64][PITCH];
-  // TR: [0] = -lse/scale, [1] = -delta of the chunk's 64 rows
+  // [0] = -lse/scale, [1] = -delta of the chunk's 64 rows
   __shared__ __attribute__((aligned(16))) float ldsL[DBUF ? 2 : 1][2][64];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1104,10 +961,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 
   // staging: same DBUF pipeline as the dV kernel (see comment there)
   bf16x8 rq[2][D / 64], rdo[2][D / 64];
-  float rl = 0.f;   // TR: wave 0 carries -lse/scale, wave 1 -delta
+  float rl = 0.f;   // wave 0 carries -lse/scale, wave 1 -delta
   const float neg_inv_scale = -1.f / scale;
   auto prefetch = [&](int64_t q0) {
-    if (TR && wave < 2) {
+    if (wave < 2) {
       const int64_t qr = q0 + lane;
       rl = (wave == 0 ? lsep : dltp)[qr < len ? qr : len - 1] *
            (wave == 0 ? neg_inv_scale : -1.f);
@@ -1126,24 +983,24 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
     }
   };
   auto commit = [&](int buf) {
-    if (TR && wave < 2) ldsL[buf][wave][lane] = rl;
+    if (wave < 2) ldsL[buf][wave][lane] = rl;
 #pragma unroll
     for (int half = 0; half < 2; ++half)
 #pragma unroll
       for (int s = 0; s < D / 64; ++s) {
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsQ[buf], stage_row + half * 32,
-                          stage_seg + s * 64)) =
+            img_at<D>(ldsQ[buf], stage_row + half * 32,
+                      stage_seg + s * 64)) =
             rq[half][s];
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsDO[buf], stage_row + half * 32,
-                          stage_seg + s * 64)) =
+            img_at<D>(ldsDO[buf], stage_row + half * 32,
+                      stage_seg + s * 64)) =
             rdo[half][s];
       }
   };
   auto stage_q64 = [&](int64_t q0) {
     __syncthreads();
-    if (TR && wave < 2) {
+    if (wave < 2) {
       const int64_t qr = q0 + lane;
       ldsL[0][wave][lane] =
           (wave == 0 ? lsep : dltp)[qr < len ? qr : len - 1] *
@@ -1156,13 +1013,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsQ[0], stage_row + half * 32,
-                          stage_seg + seg)) =
+            img_at<D>(ldsQ[0], stage_row + half * 32,
+                      stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 qp + qr * in_ss + stage_seg + seg);
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsDO[0], stage_row + half * 32,
-                          stage_seg + seg)) =
+            img_at<D>(ldsDO[0], stage_row + half * 32,
+                      stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 dop + qr * do_ss + stage_seg + seg);
       }
@@ -1172,18 +1029,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
 
   const unsigned int* maskrow =
       DROP ? mask + bh * seq * mask_w : (const unsigned int*)nullptr;
-  // one 32-row sub-tile from LDS buffer rb: new or legacy body
+  // one 32-row sub-tile from LDS buffer rb
   auto tile = [&](auto masked, int rb, int sub, int64_t q0s) {
     constexpr bool M = decltype(masked)::value;
-    if constexpr (TR)
-      dk_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
-                             &ldsL[rb][0][sub], &ldsL[rb][1][sub], sub,
-                             q0s, len, mykv, scale, causal, kfrag, vfrag,
-                             dkt, lkv, hi, maskrow, mask_w, inv_keep);
-    else
-      dk_tile<M, DROP, D>(ldsQ[rb], ldsDO[rb], sub, q0s, len, mykv, scale,
-                          causal, lsep, dltp, kfrag, vfrag, dkt, lkv, hi,
-                          maskrow, mask_w, inv_keep);
+    dk_tile_tr<M, DROP, D>(&ldsQ[rb][0][0], &ldsDO[rb][0][0],
+                           &ldsL[rb][0][sub], &ldsL[rb][1][sub], sub,
+                           q0s, len, mykv, scale, causal, kfrag, vfrag,
+                           dkt, lkv, hi, maskrow, mask_w, inv_keep);
   };
   constexpr std::true_type MASKED_T{};
   constexpr std::false_type PLAIN_T{};
@@ -1249,15 +1101,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dk_kernel(
   short* dkp = dk + (bh / heads) * g_sb + (bh % heads) * g_sh +
                mykv * g_ss;
 #pragma unroll
-  for (int dj = 0; dj < D / 32; ++dj) {
-    if constexpr (TR) {
-      store_acc_bf16(dkp + dj * 32, dkt[dj], hi);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        dkp[dj * 32 + crow(r, hi)] = (short)f2bf(dkt[dj][r]);
-    }
-  }
+  for (int dj = 0; dj < D / 32; ++dj)
+    store_acc_bf16(dkp + dj * 32, dkt[dj], hi);
 }
 
 // ============================================================================
@@ -1311,8 +1156,8 @@ DEVI void dkdv_tile_tr(const short* imgQ, const short* imgDO,
     }
   }
   const int lane = hi * 32 + lkv;
-  bf16x8 pb0 = assemble_pfrag<true>(&p[0]);
-  bf16x8 pb1 = assemble_pfrag<true>(&p[8]);
+  bf16x8 pb0 = assemble_pfrag(&p[0]);
+  bf16x8 pb1 = assemble_pfrag(&p[8]);
 #pragma unroll
   for (int qc = 0; qc < 2; ++qc) {
     bf16x8 pb = qc == 0 ? pb0 : pb1;
@@ -1323,8 +1168,8 @@ DEVI void dkdv_tile_tr(const short* imgQ, const short* imgDO,
           __builtin_amdgcn_mfma_f32_32x32x16_bf16(dot, pb, dvt[dj], 0, 0, 0);
     }
   }
-  bf16x8 db0 = assemble_pfrag<true>(&ds[0]);
-  bf16x8 db1 = assemble_pfrag<true>(&ds[8]);
+  bf16x8 db0 = assemble_pfrag(&ds[0]);
+  bf16x8 db1 = assemble_pfrag(&ds[8]);
 #pragma unroll
   for (int qc = 0; qc < 2; ++qc) {
     bf16x8 db = qc == 0 ? db0 : db1;
@@ -1463,78 +1308,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(
 }
 
 // ============================================================================
-// backward kernel B (q-parallel): dQ.  K and V tiles staged in LDS as
-// row copies per block; row fragments via ds_read_b128, K-transposed
-// fragments via 2-byte LDS reads.  Like the forward, the kv loop is
-// split into a branch-free bulk phase (below the causal diagonal /
-// inside the seq bound) and a masked diagonal+tail phase.
+// backward kernel B (q-parallel): dQ.  K and V tiles staged in LDS in
+// the dual-use image per block; row fragments via ds_read_b128,
+// K-transposed fragments via ds_read_b64_tr_b16.  Like the forward, the
+// kv loop is split into a branch-free bulk phase (below the causal
+// diagonal / inside the seq bound) and a masked diagonal+tail phase.
 // ============================================================================
 
-// one 32-key sub-tile (of the 64-row staged chunk) of the dQ loop.
+// one 32-key sub-tile (of the 64-row staged chunk) of the dQ loop; the
+// row constants (mylse, mydelta) are lane-local.
 // DROP: dS = P o (dP_d o M/(1-p) - D) — P stays undropped, the V^T dO
 // term is masked+rescaled with the forward's published keep bits.
-template <bool MASKED, bool DROP, int D>
-DEVI void dq_tile(const short (&ldsK)[64][D + 8],
-                  const short (&ldsVr)[64][D + 8],
-                  int sub, int64_t kv0, int64_t seq, int64_t myq,
-                  float scale, int causal, float mylse, float mydelta,
-                  const bf16x8 (&qfrag)[D / 16],
-                  const bf16x8 (&dofrag)[D / 16],
-                  f32x16 (&dqt)[D / 32], int lq, int hi,
-                  const unsigned int* maskrow, int64_t mask_w,
-                  float inv_keep) {
-  f32x16 st = {};
-  f32x16 dpt = {};
-#pragma unroll
-  for (int c = 0; c < D / 16; ++c) {
-    bf16x8 kf = *reinterpret_cast<const bf16x8*>(
-        &ldsK[sub + lq][hi * 8 + 16 * c]);
-    bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-        &ldsVr[sub + lq][hi * 8 + 16 * c]);
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfrag[c], st, 0, 0, 0);
-    dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dofrag[c], dpt, 0, 0,
-                                                  0);
-  }
-  unsigned int mword = 0;
-  if (DROP) {
-    const int64_t qc = myq < seq ? myq : seq - 1;
-    mword = maskrow[qc * mask_w + (kv0 >> 5)];
-  }
-  float ds[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float pv = __expf(st[r] * scale - mylse);
-    if (MASKED) {
-      const int64_t kvg = kv0 + crow(r, hi);
-      if (myq >= seq || kvg >= seq || (causal && kvg > myq)) pv = 0.f;
-    }
-    float dp = dpt[r];
-    if (DROP)
-      dp *= ((mword >> crow(r, hi)) & 1u) ? inv_keep : 0.f;
-    ds[r] = pv * (dp - mydelta) * scale;
-  }
-  bf16x8 db0 = assemble_pfrag(&ds[0]);
-  bf16x8 db1 = assemble_pfrag(&ds[8]);
-#pragma unroll
-  for (int kc = 0; kc < 2; ++kc) {
-    bf16x8 db = kc == 0 ? db0 : db1;
-#pragma unroll
-    for (int dj = 0; dj < D / 32; ++dj) {
-      bf16x8 kt;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int kr = sub + kc * 16 + hi * 8 + j;
-        kt[j] = ldsK[kr][dj * 32 + lq];
-      }
-      dqt[dj] =
-          __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt, db, dqt[dj], 0, 0, 0);
-    }
-  }
-}
-
-// new dQ tile body (see dv_tile_tr): K/V in the dual-use image, the
-// K-transposed fragments by ds_read_b64_tr_b16, hardware bf16 convert.
-// The row constants were lane-local already.
 template <bool MASKED, bool DROP, int D>
 DEVI void dq_tile_tr(const short* imgK, const short* imgV, int sub,
                      int64_t kv0, int64_t seq, int64_t myq, float scale,
@@ -1573,8 +1357,8 @@ DEVI void dq_tile_tr(const short* imgK, const short* imgV, int sub,
       dp *= ((mword >> crow(r, hi)) & 1u) ? inv_keep : 0.f;
     ds[r] = pv * (dp - mydelta) * scale;
   }
-  bf16x8 db0 = assemble_pfrag<true>(&ds[0]);
-  bf16x8 db1 = assemble_pfrag<true>(&ds[8]);
+  bf16x8 db0 = assemble_pfrag(&ds[0]);
+  bf16x8 db1 = assemble_pfrag(&ds[8]);
   const int lane = hi * 32 + lq;
 #pragma unroll
   for (int kc = 0; kc < 2; ++kc) {
@@ -1588,7 +1372,7 @@ DEVI void dq_tile_tr(const short* imgK, const short* imgV, int sub,
   }
 }
 
-template <bool DROP, bool DBUF, int D, bool TR>
+template <bool DROP, int D>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
@@ -1600,11 +1384,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     int64_t o_ss, const unsigned int* __restrict__ mask, int64_t mask_w,
     float inv_keep, const float* __restrict__ dlse,
     const int* __restrict__ seqlens) {
-  constexpr int PITCH = TR ? img_pitch<D>() : D + 8;
-  __shared__ __attribute__((aligned(16))) short
-      ldsK[DBUF ? 2 : 1][64][PITCH];
-  __shared__ __attribute__((aligned(16))) short
-      ldsVr[DBUF ? 2 : 1][64][PITCH];
+  __shared__ __attribute__((aligned(16))) short ldsK[64][img_pitch<D>()];
+  __shared__ __attribute__((aligned(16))) short ldsVr[64][img_pitch<D>()];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
@@ -1681,13 +1462,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
 #pragma unroll
       for (int seg = 0; seg < D; seg += 64) {
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsK[0], stage_row + half * 32,
-                          stage_seg + seg)) =
+            img_at<D>(ldsK, stage_row + half * 32, stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 kp + kr * in_ss + stage_seg + seg);
         *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsVr[0], stage_row + half * 32,
-                          stage_seg + seg)) =
+            img_at<D>(ldsVr, stage_row + half * 32, stage_seg + seg)) =
             *reinterpret_cast<const bf16x8*>(
                 vp + kr * in_ss + stage_seg + seg);
       }
@@ -1695,115 +1474,42 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_bwd_dq_kernel(
     __syncthreads();
   };
 
-  // DBUF: same register-double-buffered single-barrier pipeline as the
-  // dV/dK kernels (next kv chunk prefetched into VGPRs during this
-  // chunk's MFMAs; see attn_bwd_dv_kernel).
-  bf16x8 rk[2][D / 64], rv[2][D / 64];
-  auto prefetch = [&](int64_t kv0) {
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      int64_t kr = kv0 + stage_row + half * 32;
-      if (kr >= len) kr = len - 1;
-#pragma unroll
-      for (int s = 0; s < D / 64; ++s) {
-        rk[half][s] = *reinterpret_cast<const bf16x8*>(
-            kp + kr * in_ss + stage_seg + s * 64);
-        rv[half][s] = *reinterpret_cast<const bf16x8*>(
-            vp + kr * in_ss + stage_seg + s * 64);
-      }
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int s = 0; s < D / 64; ++s) {
-        *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsK[buf], stage_row + half * 32,
-                          stage_seg + s * 64)) =
-            rk[half][s];
-        *reinterpret_cast<bf16x8*>(
-            img_at<TR, D>(ldsVr[buf], stage_row + half * 32,
-                          stage_seg + s * 64)) =
-            rv[half][s];
-      }
-  };
-
   const unsigned int* maskrow =
       DROP ? mask + bh * seq * mask_w : (const unsigned int*)nullptr;
-  // one 32-key sub-tile from LDS buffer rb: new or legacy body
-  auto tile = [&](auto masked, int rb, int sub, int64_t kvs) {
+  // one 32-key sub-tile of the staged chunk
+  auto tile = [&](auto masked, int sub, int64_t kvs) {
     constexpr bool M = decltype(masked)::value;
-    if constexpr (TR)
-      dq_tile_tr<M, DROP, D>(&ldsK[rb][0][0], &ldsVr[rb][0][0], sub, kvs,
-                             len, myq, scale, causal, mylse, mydelta,
-                             qfrag, dofrag, dqt, lq, hi, maskrow, mask_w,
-                             inv_keep);
-    else
-      dq_tile<M, DROP, D>(ldsK[rb], ldsVr[rb], sub, kvs, len, myq, scale,
-                          causal, mylse, mydelta, qfrag, dofrag, dqt, lq,
-                          hi, maskrow, mask_w, inv_keep);
+    dq_tile_tr<M, DROP, D>(&ldsK[0][0], &ldsVr[0][0], sub, kvs, len, myq,
+                           scale, causal, mylse, mydelta, qfrag, dofrag,
+                           dqt, lq, hi, maskrow, mask_w, inv_keep);
   };
   constexpr std::true_type MASKED_T{};
   constexpr std::false_type PLAIN_T{};
-  if (!DBUF) {
-    int64_t kv0 = 0;
-    for (; kv0 < bulk_end; kv0 += 64) {
-      stage_kv64(kv0);
+  int64_t kv0 = 0;
+  for (; kv0 < bulk_end; kv0 += 64) {
+    stage_kv64(kv0);
 #pragma unroll
-      for (int sub = 0; sub < 64; sub += 32)
-        tile(PLAIN_T, 0, sub, kv0 + sub);
-    }
-    for (; kv0 < blk_kv_end; kv0 += 64) {
-      stage_kv64(kv0);
-      const int64_t wave_kv_end = causal
-          ? (q0 + 32 < len ? q0 + 32 : len) : len;
-      if (!active) continue;
+    for (int sub = 0; sub < 64; sub += 32)
+      tile(PLAIN_T, sub, kv0 + sub);
+  }
+  for (; kv0 < blk_kv_end; kv0 += 64) {
+    stage_kv64(kv0);
+    const int64_t wave_kv_end = causal
+        ? (q0 + 32 < len ? q0 + 32 : len) : len;
+    if (!active) continue;
 #pragma unroll
-      for (int sub = 0; sub < 64; sub += 32) {
-        const int64_t kvs = kv0 + sub;
-        if (kvs >= wave_kv_end) break;
-        tile(MASKED_T, 0, sub, kvs);
-      }
-    }
-  } else {
-    int buf = 0;
-    prefetch(0);
-    for (int64_t kv0 = 0; kv0 < blk_kv_end; kv0 += 64) {
-      commit(buf);
-      __syncthreads();
-      if (kv0 + 64 < blk_kv_end) prefetch(kv0 + 64);
-      const int rb = buf;
-      buf ^= 1;
-      if (kv0 < bulk_end) {
-#pragma unroll
-        for (int sub = 0; sub < 64; sub += 32)
-          tile(PLAIN_T, rb, sub, kv0 + sub);
-      } else if (active) {
-        const int64_t wave_kv_end = causal
-            ? (q0 + 32 < len ? q0 + 32 : len) : len;
-#pragma unroll
-        for (int sub = 0; sub < 64; sub += 32) {
-          const int64_t kvs = kv0 + sub;
-          if (kvs >= wave_kv_end) break;
-          tile(MASKED_T, rb, sub, kvs);
-        }
-      }
+    for (int sub = 0; sub < 64; sub += 32) {
+      const int64_t kvs = kv0 + sub;
+      if (kvs >= wave_kv_end) break;
+      tile(MASKED_T, sub, kvs);
     }
   }
 
   if (!active || myq >= len) return;
   short* dqp = dq + (bh / heads) * g_sb + (bh % heads) * g_sh + myq * g_ss;
 #pragma unroll
-  for (int dj = 0; dj < D / 32; ++dj) {
-    if constexpr (TR) {
-      store_acc_bf16(dqp + dj * 32, dqt[dj], hi);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        dqp[dj * 32 + crow(r, hi)] = (short)f2bf(dqt[dj][r]);
-    }
-  }
+  for (int dj = 0; dj < D / 32; ++dj)
+    store_acc_bf16(dqp + dj * 32, dqt[dj], hi);
 }
 
 }  // namespace
@@ -1896,9 +1602,10 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
       g_strides[2], drop_mask, mask_w, inv_keep, seqlens
     // d64 staging mode (EPL_ATTN_BWD_DBUF): 0 = two-barrier direct
     // staging; 1 = dV double-buffered single-barrier pipeline
-    // (spill-free); 2 = dK pipelined too (spills 12-40 VGPRs at 3
-    // waves but still wins on long q loops); 3 = dQ pipelined too
-    // (spills 68 B/lane at 3 waves).
+    // (spill-free); 2 (or more) = dK pipelined too (spills 12-40 VGPRs
+    // at 3 waves but still wins on long q loops).  dQ always stages
+    // directly: its pipelined form lost both A/Bs
+    // (profiles/r02_dbuf_ab.txt).
     // Default -1 = auto: non-causal runs mode 2 (same-box A/B in
     // profiles/r02_dbuf_ab.txt: bert s512 -7.6%, s4096 -9.9%), causal
     // keeps direct staging (its per-block q loop is half as long and
@@ -1911,36 +1618,21 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
     const int mode = dbuf_mode < 0 ? (causal ? 0 : 2) : dbuf_mode;
     const bool dbuf = mode >= 1;
     const bool dbuf_k = mode >= 2;
-    const bool dbuf_q = mode >= 3;
-    // tile bodies (EPL_ATTN_BWD_TILES): default = transposed-LDS-read
-    // tiles; "legacy" = the previous bodies, kept for a same-process
-    // A/B until a second independent run confirms the numbers
-    static const bool legacy_tiles = [] {
-      const char* e = getenv("EPL_ATTN_BWD_TILES");
-      return e != nullptr && strcmp(e, "legacy") == 0;
-    }();
-    auto launch3 = [&](auto drop_c, auto d_c, auto tr_c) {
+    auto launch = [&](auto drop_c, auto d_c) {
       constexpr bool DROP = decltype(drop_c)::value;
       constexpr int D = decltype(d_c)::value;
-      constexpr bool TR = decltype(tr_c)::value;
       if (fused) {
         // nothing to launch ahead of dQ
       } else if (D == 64 && dbuf)
         hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, D == 64, D, TR>), grid,
+            HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, D == 64, D>), grid,
             dim3(256), 0, stream, DV_ARGS);
       else
         hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, false, D, TR>), grid,
+            HIP_KERNEL_NAME(attn_bwd_dv_kernel<DROP, false, D>), grid,
             dim3(256), 0, stream, DV_ARGS);
-      if (D == 64 && dbuf_q)
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<DROP, D == 64, D, TR>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
-      else
-        hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dq_kernel<DROP, false, D, TR>), grid,
-            dim3(256), 0, stream, DQ_ARGS);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_bwd_dq_kernel<DROP, D>), grid,
+                         dim3(256), 0, stream, DQ_ARGS);
       if (fused)
         hipLaunchKernelGGL(
             attn_bwd_dkdv_kernel, grid, dim3(256), 0, stream,
@@ -1954,30 +1646,24 @@ void epl_attn_bwd(const void* q, const void* k, const void* v,
             g_strides[1], g_strides[2], seqlens);
       else if (D == 64 && dbuf_k)
         hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, D == 64, D, TR>), grid,
+            HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, D == 64, D>), grid,
             dim3(256), 0, stream, DK_ARGS);
       else
         hipLaunchKernelGGL(
-            HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, false, D, TR>), grid,
+            HIP_KERNEL_NAME(attn_bwd_dk_kernel<DROP, false, D>), grid,
             dim3(256), 0, stream, DK_ARGS);
-    };
-    auto launch2 = [&](auto drop_c, auto d_c) {
-      if (legacy_tiles)
-        launch3(drop_c, d_c, std::false_type{});
-      else
-        launch3(drop_c, d_c, std::true_type{});
     };
     using d64 = std::integral_constant<int, 64>;
     using d128 = std::integral_constant<int, 128>;
     if (head_dim == 128) {
       if (drop_mask != nullptr)
-        launch2(std::true_type{}, d128{});
+        launch(std::true_type{}, d128{});
       else
-        launch2(std::false_type{}, d128{});
+        launch(std::false_type{}, d128{});
     } else if (drop_mask != nullptr) {
-      launch2(std::true_type{}, d64{});
+      launch(std::true_type{}, d64{});
     } else {
-      launch2(std::false_type{}, d64{});
+      launch(std::false_type{}, d64{});
     }
 #undef DV_ARGS
 #undef DQ_ARGS

@@ -1,5 +1,5 @@
 // Dual-use LDS image of a [64][D] bf16 tile for the attention kernels
-// (the backward's new tile bodies; the forward's V tile, of which only
+// (the backward's tile bodies; the forward's V tile, of which only
 // the transposed read is used) and the tr_read_probe kernel that checks
 // it.
 //
@@ -57,8 +57,8 @@ __device__ __forceinline__ s16x8 tr_frag(const short* img, int r0, int dj,
   return __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// the same fragment by eight 2-byte reads (the definition tr_frag must
-// reproduce; what the legacy tile bodies do on their padded rows)
+// the same fragment by eight 2-byte reads: the definition tr_frag must
+// reproduce, used by tr_read_probe only
 template <int D>
 __device__ __forceinline__ s16x8 gather_frag(const short* img, int r0,
                                              int dj, int lane) {

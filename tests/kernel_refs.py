@@ -423,6 +423,12 @@ ATTN_DROP_FAMILY = {1: "randn", 128: "peaked", 255: "shifted"}
 ATTN_DLSE_SEQS = (72, 200)
 ATTN_COMBINED_SEQS = (33, 64, 72, 200, 257)
 ATTN_ENV_SEQS = (72, 200, 257)
+# the autograd entry points (test_attention_bwd_tiles_gpu.py), randn only:
+# one chunk with waves 2 and 3 inactive; an 8-row tail (clamped rows under
+# the transposed read); a tail inside the second 128-key block; two
+# blocks, bulk phase only.  The dropout case is (d, seq, causal, thresh).
+ATTN_AUTOGRAD_SEQS = (64, 72, 200, 256)
+ATTN_AUTOGRAD_DROP = (64, 200, False, 128)
 ATTN_OUTPUTS = ("out", "lse", "delta", "dq", "dk", "dv")
 # allowed err / E: the derived bound is proven at 1 x E for the rounding
 # model on the CPU; the kernels get twice that on the bf16 outputs

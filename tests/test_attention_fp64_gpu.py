@@ -18,10 +18,9 @@ case asserts
 Each case prints its worst err / E per output (``ATTN-RATIO`` lines; the
 table in docs/testing.md is made from them).
 
-EPL_ATTN_BWD_TILES and EPL_ATTN_BWD_DBUF are read once per process, so the
-environment-selected paths run in fresh child processes, six side by
-side, which write their ratios to JSON; the parent applies the same
-criterion.
+EPL_ATTN_BWD_DBUF is read once per process, so the environment-selected
+staging modes run in fresh child processes, three side by side, which
+write their ratios to JSON; the parent applies the same criterion.
 """
 
 import json
@@ -316,10 +315,9 @@ def test_grid_limits_are_refused(b, h, seq, causal):
 
 
 # --------------------------------------------------------------------------
-# environment-selected tile bodies and staging modes: one child each
+# environment-selected staging modes: one child each
 # --------------------------------------------------------------------------
-SETTINGS = [("new", 0), ("new", 1), ("new", 2), ("new", 3),
-            ("legacy", 0), ("legacy", 2)]
+SETTINGS = [0, 1, 2]
 
 
 def _worker(out_path):
@@ -341,39 +339,37 @@ def _worker(out_path):
 
 @pytest.fixture(scope="module")
 def env_results(tmp_path_factory):
-    """{(tiles, dbuf): {case: {ratios, bad}}} — six children side by side"""
+    """{dbuf: {case: {ratios, bad}}} — three children side by side"""
     tmp = tmp_path_factory.mktemp("attn_fp64")
     procs = []
-    for tiles, dbuf in SETTINGS:
+    for dbuf in SETTINGS:
         env = dict(os.environ)
-        env.pop("EPL_ATTN_BWD_TILES", None)
-        if tiles == "legacy":
-            env["EPL_ATTN_BWD_TILES"] = "legacy"
         env["EPL_ATTN_BWD_DBUF"] = str(dbuf)
-        out = tmp / "{}_{}.json".format(tiles, dbuf)
+        out = tmp / "dbuf{}.json".format(dbuf)
         cmd = [sys.executable]
         if sys.flags.no_user_site:
             cmd.append("-s")
         cmd += [os.path.abspath(__file__), "--worker", str(out)]
-        procs.append((tiles, dbuf, out, subprocess.Popen(
+        procs.append((dbuf, out, subprocess.Popen(
             cmd, env=env, cwd=REPO, stdout=subprocess.PIPE,
             stderr=subprocess.STDOUT, text=True)))
     res = {}
-    for tiles, dbuf, out, p in procs:
+    for dbuf, out, p in procs:
         log, _ = p.communicate(timeout=600)
-        assert p.returncode == 0, (tiles, dbuf, log[-3000:])
+        assert p.returncode == 0, (dbuf, log[-3000:])
         with open(out) as f:
-            res[(tiles, dbuf)] = json.load(f)
+            res[dbuf] = json.load(f)
     return res
 
 
-@pytest.mark.parametrize("tiles,dbuf", SETTINGS)
-def test_env_selected_paths(env_results, tiles, dbuf):
-    res = env_results[(tiles, dbuf)]
+@pytest.mark.parametrize("dbuf", SETTINGS,
+                         ids=["dbuf{}".format(s) for s in SETTINGS])
+def test_env_selected_paths(env_results, dbuf):
+    res = env_results[dbuf]
     assert len(res) == len(kr.attn_env_cases(dbuf))
     failures = []
     for label, r in res.items():
-        report("{}-dbuf{}".format(tiles, dbuf), label, r["ratios"])
+        report("dbuf{}".format(dbuf), label, r["ratios"])
         # the same criterion as in-process, applied to the child's figures
         bad = [name for name, x in r["ratios"].items()
                if not x <= kr.ATTN_FACTOR[name]]

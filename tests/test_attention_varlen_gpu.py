@@ -17,7 +17,7 @@ asserts
 
 ``ATTN-RATIO varlen...`` lines carry the worst err / E per output (the
 table in docs/testing.md is made from them).  The environment-selected
-tile bodies and staging modes run in fresh child processes, side by side.
+staging modes run in fresh child processes, side by side.
 """
 
 import json
@@ -332,10 +332,9 @@ def test_binding_refuses_bad_seqlens():
 
 
 # --------------------------------------------------------------------------
-# environment-selected tile bodies and staging modes: one child each
+# environment-selected staging modes: one child each
 # --------------------------------------------------------------------------
-SETTINGS = [("new", 0), ("new", 1), ("new", 2), ("new", 3),
-            ("legacy", 0), ("legacy", 2)]
+SETTINGS = [0, 1, 2]
 
 
 def _worker(out_path):
@@ -358,39 +357,37 @@ def _worker(out_path):
 
 @pytest.fixture(scope="module")
 def env_results(tmp_path_factory):
-    """{(tiles, dbuf): {case: {ratios, bad}}} — six children side by side"""
+    """{dbuf: {case: {ratios, bad}}} — three children side by side"""
     tmp = tmp_path_factory.mktemp("attn_varlen")
     procs = []
-    for tiles, dbuf in SETTINGS:
+    for dbuf in SETTINGS:
         env = dict(os.environ)
-        env.pop("EPL_ATTN_BWD_TILES", None)
-        if tiles == "legacy":
-            env["EPL_ATTN_BWD_TILES"] = "legacy"
         env["EPL_ATTN_BWD_DBUF"] = str(dbuf)
-        out = tmp / "{}_{}.json".format(tiles, dbuf)
+        out = tmp / "dbuf{}.json".format(dbuf)
         cmd = [sys.executable]
         if sys.flags.no_user_site:
             cmd.append("-s")
         cmd += [os.path.abspath(__file__), "--worker", str(out)]
-        procs.append((tiles, dbuf, out, subprocess.Popen(
+        procs.append((dbuf, out, subprocess.Popen(
             cmd, env=env, cwd=REPO, stdout=subprocess.PIPE,
             stderr=subprocess.STDOUT, text=True)))
     res = {}
-    for tiles, dbuf, out, p in procs:
+    for dbuf, out, p in procs:
         log, _ = p.communicate(timeout=600)
-        assert p.returncode == 0, (tiles, dbuf, log[-3000:])
+        assert p.returncode == 0, (dbuf, log[-3000:])
         with open(out) as f:
-            res[(tiles, dbuf)] = json.load(f)
+            res[dbuf] = json.load(f)
     return res
 
 
-@pytest.mark.parametrize("tiles,dbuf", SETTINGS)
-def test_env_selected_paths(env_results, tiles, dbuf):
-    res = env_results[(tiles, dbuf)]
+@pytest.mark.parametrize("dbuf", SETTINGS,
+                         ids=["dbuf{}".format(s) for s in SETTINGS])
+def test_env_selected_paths(env_results, dbuf):
+    res = env_results[dbuf]
     assert len(res) == len(vr.env_cases(dbuf))
     failures = []
     for label, r in res.items():
-        report("varlen-{}-dbuf{}".format(tiles, dbuf), label, r["ratios"])
+        report("varlen-dbuf{}".format(dbuf), label, r["ratios"])
         # the same criterion as in-process, applied to the child's figures
         bad = [name for name, x in r["ratios"].items()
                if not x <= kr.ATTN_FACTOR[name]]

@@ -402,6 +402,17 @@ def test_attn_emulation_inside_bounds_env_cases():
     print(worst)
 
 
+def test_attn_emulation_inside_bounds_autograd_cases():
+    worst = {}
+    cases = [(d, seq, causal, 0) for d in kr.ATTN_DIMS
+             for seq in kr.ATTN_AUTOGRAD_SEQS for causal in (False, True)]
+    for d, seq, causal, thresh in cases + [kr.ATTN_AUTOGRAD_DROP]:
+        _assert_emulation_inside(
+            (d, seq, causal, thresh),
+            _attn_case("randn", seq, d, causal, thresh) + (causal,), worst)
+    print(worst)
+
+
 ATTN_MUTATIONS = (
     "causal_ge", "last_key_dropped", "padding_key_counted",
     "v_rows_exchanged", "bh_transposed", "keep_from_neighbour_key",
