@@ -81,13 +81,15 @@ void epl_attn_fwd(const void*, const void*, const void*, void*, float*,
                   int64_t, int64_t, float, bool, int64_t, int64_t,
                   const int64_t*,
                   const int64_t*, unsigned int*, int64_t,
-                  unsigned long long, int, float, const int*, hipStream_t);
+                  unsigned long long, int, float, const int*, int64_t,
+                  const int64_t*, hipStream_t);
 void epl_attn_bwd(const void*, const void*, const void*, const void*,
                   const void*, const float*, float*, void*, void*, void*,
                   int64_t, int64_t, float, bool, int64_t, const int64_t*,
                   const int64_t*, const int64_t*, const int64_t*, int,
                   const unsigned int*, int64_t, float, int64_t,
-                  const float*, const int*, hipStream_t);
+                  const float*, const int*, int64_t, const int64_t*,
+                  const int64_t*, hipStream_t);
 void epl_rms_norm_fwd(void*, const void*, const void*, void*, const void*,
                       float*, int64_t, int64_t, float, hipStream_t);
 int64_t epl_rms_norm_bwd_parts(int64_t, int64_t);
@@ -561,7 +563,8 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
                lse.data_ptr<float>(), bh, seq, (float)scale, causal, heads,
                head_dim, in_s, o_s, mptr, mask_w,
                (unsigned long long)seed, (int)drop_thresh,
-               (float)inv_keep, attn_seqlens(seqlens, q), cur_stream());
+               (float)inv_keep, attn_seqlens(seqlens, q), heads, in_s,
+               cur_stream());
 }
 
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
@@ -605,7 +608,124 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
                dv.data_ptr(), bh, seq, (float)scale, causal, heads, in_s,
                o_s, do_s, g_s, split_dkdv ? 1 : 0, mptr, mask_w,
                (float)inv_keep, q.size(3), dlse_ptr,
-               attn_seqlens(seqlens, q), cur_stream());
+               attn_seqlens(seqlens, q), heads, in_s, g_s, cur_stream());
+}
+
+// Grouped-query attention: q, out, dout, dq are [B, H, S, D]; k, v (and
+// dk, dv) are [B, Hkv, S, D] with strides of their own, H % Hkv == 0, and
+// query head h reads kv head h / (H / Hkv).  No dropout and no dlse.
+// Returns Hkv.  Equal head counts run the MHA kernels, which want one
+// stride triplet for q, k and v.
+static int64_t attn_gqa_shapes(const at::Tensor& q, const at::Tensor& k,
+                               const at::Tensor& v, int64_t* kv_s,
+                               const char* kname, const char* vname,
+                               const int64_t* q_s, bool causal) {
+  int64_t tmp[3];
+  attn_strides(k, kv_s, kname);
+  attn_strides(v, tmp, vname);
+  TORCH_CHECK(tmp[0] == kv_s[0] && tmp[1] == kv_s[1] && tmp[2] == kv_s[2],
+              kname, "/", vname, " must share strides");
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0) &&
+                  k.size(2) == q.size(2) && k.size(3) == q.size(3),
+              kname, "/", vname, " must be [B, Hkv, S, D] of q's B, S, D");
+  const int64_t heads = q.size(1), kv_heads = k.size(1);
+  TORCH_CHECK(kv_heads >= 1 && heads % kv_heads == 0, "query heads ", heads,
+              " must be a multiple of kv heads ", kv_heads);
+  if (kv_heads == heads)
+    TORCH_CHECK(kv_s[0] == q_s[0] && kv_s[1] == q_s[1] && kv_s[2] == q_s[2],
+                "equal head counts: q/k/v must share strides");
+  const int64_t seq = q.size(2);
+  attn_check_grid(q.size(0) * heads, seq, causal);
+  attn_check_grid(q.size(0) * kv_heads, seq, causal);
+  // the non-causal q-parallel GQA grid carries n * G blocks on x and the
+  // block order's linear ids are 32-bit (attn_block_order.h)
+  TORCH_CHECK(causal || (seq + 127) / 128 * (heads / kv_heads) <= 65535,
+              "attention: seq ", seq, " x group ", heads / kv_heads,
+              " exceeds the 65535 blocks of a batch-kv-head");
+  return kv_heads;
+}
+
+void attn_fwd_gqa(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
+                  at::Tensor lse, double scale, bool causal,
+                  c10::optional<at::Tensor> seqlens) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
+              k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16);
+  int64_t in_s[3], kv_s[3], o_s[3];
+  attn_strides(q, in_s, "q");
+  attn_strides(out, o_s, "out");
+  const int64_t kv_heads =
+      attn_gqa_shapes(q, k, v, kv_s, "k", "v", in_s, causal);
+  TORCH_CHECK(out.sizes() == q.sizes(), "out must have q's shape");
+  check(lse, at::kFloat, "lse");
+  const int64_t heads = q.size(1), seq = q.size(2);
+  TORCH_CHECK(lse.numel() == q.size(0) * heads * seq, "lse size mismatch");
+  epl_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+               lse.data_ptr<float>(), q.size(0) * heads, seq, (float)scale,
+               causal, heads, q.size(3), in_s, o_s, nullptr,
+               (seq + 31) / 32, 0ull, 0, 1.f, attn_seqlens(seqlens, q),
+               kv_heads, kv_s, cur_stream());
+}
+
+void attn_bwd_gqa(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
+                  at::Tensor dout, at::Tensor lse, at::Tensor delta_ws,
+                  at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
+                  bool causal, c10::optional<at::Tensor> seqlens) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
+              k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16 &&
+              dk.scalar_type() == at::kBFloat16 &&
+              dv.scalar_type() == at::kBFloat16);
+  int64_t in_s[3], kv_s[3], o_s[3], do_s[3], g_s[3], gkv_s[3];
+  attn_strides(q, in_s, "q");
+  attn_strides(out, o_s, "out");
+  attn_strides(dout, do_s, "dout");
+  attn_strides(dq, g_s, "dq");
+  const int64_t kv_heads =
+      attn_gqa_shapes(q, k, v, kv_s, "k", "v", in_s, causal);
+  attn_gqa_shapes(q, dk, dv, gkv_s, "dk", "dv", g_s, causal);
+  TORCH_CHECK(dk.sizes() == k.sizes(), "dk/dv must have k's shape");
+  TORCH_CHECK(out.sizes() == q.sizes() && dout.sizes() == q.sizes() &&
+              dq.sizes() == q.sizes(), "out/dout/dq must have q's shape");
+  check(lse, at::kFloat, "lse");
+  check(delta_ws, at::kFloat, "delta_ws");
+  const int64_t heads = q.size(1), seq = q.size(2);
+  TORCH_CHECK(lse.numel() == q.size(0) * heads * seq &&
+              delta_ws.numel() == lse.numel(), "lse/delta_ws size mismatch");
+  epl_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+               dout.data_ptr(), lse.data_ptr<float>(),
+               delta_ws.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+               dv.data_ptr(), q.size(0) * heads, seq, (float)scale, causal,
+               heads, in_s, o_s, do_s, g_s, 1, nullptr, (seq + 31) / 32,
+               1.f, q.size(3), nullptr, attn_seqlens(seqlens, q), kv_heads,
+               kv_s, gkv_s, cur_stream());
+}
+
+// the group-aware block orders of the q-parallel GQA grids evaluated on
+// the host: non-causal int32 [n * G * BHkv, 2] (bh, blk) at each linear
+// id x + n * G * y; causal int32 [G * BHkv] bh at each x
+at::Tensor attn_gqa_order_host(int64_t n, int64_t bhkv, int64_t group,
+                               bool causal) {
+  TORCH_CHECK(n >= 1 && bhkv >= 1 && group >= 1 && n * group <= 65535 &&
+                  bhkv * group <= 65535, "grid dimensions out of range");
+  if (causal) {
+    at::Tensor out = at::empty({group * bhkv}, at::kInt);
+    for (int64_t x = 0; x < group * bhkv; ++x)
+      out.data_ptr<int>()[x] = (int)attn_order::causal_group_bh(
+          (unsigned)x, (unsigned)group, (unsigned)bhkv);
+    return out;
+  }
+  at::Tensor out = at::empty({n * group * bhkv, 2}, at::kInt);
+  int* p = out.data_ptr<int>();
+  for (int64_t y = 0; y < bhkv; ++y)
+    for (int64_t x = 0; x < n * group; ++x) {
+      const attn_order::Block b = attn_order::block_of_group(
+          (unsigned)x, (unsigned)y, (unsigned)n, (unsigned)group,
+          (unsigned)bhkv);
+      p[2 * (x + n * group * y)] = (int)b.bh;
+      p[2 * (x + n * group * y) + 1] = (int)b.blk;
+    }
+  return out;
 }
 
 // out_gather / out_tr: int16 [4 * head_dim/32, 64, 8] (fragment, lane,
@@ -1037,6 +1157,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale"), py::arg("causal"), py::arg("split_dkdv"),
         py::arg("drop_mask"), py::arg("inv_keep"), py::arg("dlse"),
         py::arg("seqlens") = py::none());
+  m.def("attn_fwd_gqa", &attn_fwd_gqa, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("scale"),
+        py::arg("causal"), py::arg("seqlens") = py::none());
+  m.def("attn_bwd_gqa", &attn_bwd_gqa, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("delta_ws"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("scale"), py::arg("causal"),
+        py::arg("seqlens") = py::none());
+  m.def("attn_gqa_order_host", &attn_gqa_order_host);
   m.def("rms_norm_fwd", &rms_norm_fwd, py::arg("out"), py::arg("x"),
         py::arg("res"), py::arg("s"), py::arg("gamma"), py::arg("rstd"),
         py::arg("eps"));

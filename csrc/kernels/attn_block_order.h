@@ -58,4 +58,60 @@ __host__ __device__ inline Block block_of(unsigned int x, unsigned int y,
   return b;
 }
 
+// ---------------------------------------------------------------------------
+// Grouped-query attention: H = G * Hkv query heads, query head h reads kv
+// head h / G, so the G heads of a group read the same K and V.  With
+// bkv = b * Hkv + kvh the query batch-head is bh = bkv * G + g.  The
+// q-parallel GQA kernels (forward, dQ) want a group's blocks in one L2.
+//
+// Non-causal, dim3(n * G, B * Hkv): block_of() at kv-head granularity with
+// n * G blocks per batch-kv-head,
+//
+//   (bkv, j) = block_of(x, y, n * G, B * Hkv)
+//   bh = bkv * G + j / n,  blk = j % n
+//
+// Bijection onto [0, B * H) x [0, n): block_of is one onto
+// [0, B * Hkv) x [0, n * G) (above), and j -> (j / n, j % n) is one from
+// [0, n * G) onto [0, G) x [0, n); (bkv, g) -> bkv * G + g is one from
+// [0, B * Hkv) x [0, G) onto [0, B * H).  A group's n * G blocks follow
+// each other on one XCD, head after head.
+//
+// Causal, dim3(B * H, n): the blocks of one y row (one q-block index, all
+// batch-heads) are handed out x-fastest, so the heads that run together
+// are neighbours in x, round-robin over the XCDs.  causal_group_bh() maps
+// x to bh so that the G heads of a group share x % 8:
+//
+//   BKV8 = (B * Hkv) & ~7
+//   x <  8 * G * (BKV8 / 8):  c = x % 8, j = x / 8:
+//                             bkv = (j / G) * 8 + c,  bh = bkv * G + j % G
+//   x >= G * BKV8:            bh = x                          (identity)
+//
+// Bijection onto [0, B * H): G * BKV8 is a multiple of 8, so the x below
+// it are exactly the pairs (c, j) with 0 <= c < 8, 0 <= j < G * BKV8 / 8
+// (x = 8 j + c).  Write j = G t + r with 0 <= r < G; then
+// 0 <= t < BKV8 / 8, bkv = 8 t + c runs over [0, BKV8) with the inverse
+// c = bkv % 8, t = bkv / 8, and bh = bkv * G + r covers [0, G * BKV8)
+// once each.  The x from G * BKV8 to B * H - 1 keep themselves.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline Block block_of_group(unsigned int x,
+                                                unsigned int y,
+                                                unsigned int n,
+                                                unsigned int G,
+                                                unsigned int BHkv) {
+  const Block kv = block_of(x, y, n * G, BHkv);
+  Block b;
+  b.bh = kv.bh * G + kv.blk / n;
+  b.blk = kv.blk % n;
+  return b;
+}
+
+__host__ __device__ inline unsigned int causal_group_bh(unsigned int x,
+                                                        unsigned int G,
+                                                        unsigned int BHkv) {
+  const unsigned int lim = G * (BHkv & ~7u);
+  if (x >= lim) return x;
+  const unsigned int c = x & 7u, j = x >> 3;
+  return ((j / G) * 8u + c) * G + j % G;
+}
+
 }  // namespace attn_order

@@ -10,9 +10,13 @@ buffer; no unbind, no copy), and FusedSwiGLU on the packed gate/up GEMM
 output.  Shapes the kernels do not take (fp32, CPU, head_dim other than
 64 / 128) run apply_rope + flash_attention and the torch compositions.
 
-Out of scope: grouped-query attention (the attention kernels take equal
-q and kv head counts; Llama-2-7B, the largest config here, is MHA), tensor
--parallel sharding of the packed gate/up weight, and a bench.py config.
+Grouped-query attention (``kv_heads`` in a config, ``num_kv_heads`` on the
+modules): one packed projection of H query, Hkv key and Hkv value heads;
+the GQA flash kernels read K / V once per group and sum dK / dV over the
+group in registers (docs/kernels.md), nothing is expanded.
+
+Out of scope: tensor-parallel sharding of the packed qkv and gate/up
+weights, KV-cache decoding, and a bench.py config.
 """
 
 import torch.nn as nn
@@ -29,19 +33,34 @@ LLAMA_CONFIGS = {
     "llama-1b": dict(layers=16, hidden=2048, heads=16, ffn=5632),
     # Llama-2-7B exactly (MHA)
     "llama-7b": dict(layers=32, hidden=4096, heads=32, ffn=11008),
+    "llama-tiny-gqa": dict(layers=2, hidden=128, heads=2, kv_heads=1,
+                           ffn=352),
+    # Llama-3-8B (GQA, 4 query heads per kv head); callers pass
+    # rope_theta=500000.0 and vocab_size=128256
+    "llama3-8b": dict(layers=32, hidden=4096, heads=32, kv_heads=8,
+                      ffn=14336),
 }
 
 
 class LlamaAttention(nn.Module):
-    """Causal self-attention with rotary q / k; bias-free projections."""
+    """Causal self-attention with rotary q / k; bias-free projections.
+    ``num_kv_heads`` < ``num_heads`` is grouped-query attention: the one
+    packed projection emits H query, Hkv key and Hkv value heads, and
+    query head h attends kv head h // (H // Hkv)."""
 
-    def __init__(self, hidden, num_heads, rope_theta=10000.0):
+    def __init__(self, hidden, num_heads, num_kv_heads=None,
+                 rope_theta=10000.0):
         super().__init__()
         assert hidden % num_heads == 0
         self.num_heads = num_heads
+        self.num_kv_heads = num_heads if num_kv_heads is None \
+            else num_kv_heads
+        assert num_heads % self.num_kv_heads == 0
         self.head_dim = hidden // num_heads
         self.rope_theta = rope_theta
-        self.qkv = nn.Linear(hidden, 3 * hidden, bias=False)
+        self.qkv = nn.Linear(
+            hidden, (num_heads + 2 * self.num_kv_heads) * self.head_dim,
+            bias=False)
         self.proj = nn.Linear(hidden, hidden, bias=False)
 
     def forward(self, x):
@@ -50,15 +69,17 @@ class LlamaAttention(nn.Module):
             apply_rope, rope_qkv_flash_attention, rope_qkv_native_ok)
         b, s, h = x.shape
         qkv = self.qkv(x)
-        if rope_qkv_native_ok(qkv, self.num_heads):
+        hq, hkv = self.num_heads, self.num_kv_heads
+        if rope_qkv_native_ok(qkv, hq, hkv):
             # q and k rotated in place in the projection's own output,
             # the attention kernels read its strided slices
             o = rope_qkv_flash_attention(qkv, causal=True,
                                          theta=self.rope_theta,
-                                         num_heads=self.num_heads)
+                                         num_heads=hq, num_kv_heads=hkv)
         else:
             q, k, v = (t.transpose(1, 2) for t in qkv.reshape(
-                b, s, 3, self.num_heads, self.head_dim).unbind(dim=2))
+                b, s, hq + 2 * hkv, self.head_dim).split(
+                    [hq, hkv, hkv], dim=2))
             q = apply_rope(q, theta=self.rope_theta)
             k = apply_rope(k, theta=self.rope_theta)
             o = flash_attention(q, k, v, causal=True)
@@ -67,10 +88,11 @@ class LlamaAttention(nn.Module):
 
 class LlamaBlock(nn.Module):
     def __init__(self, hidden, num_heads, ffn_hidden, rope_theta=10000.0,
-                 eps=1e-5):
+                 eps=1e-5, num_kv_heads=None):
         super().__init__()
         self.rms1 = FusedRMSNorm(hidden, eps=eps)
-        self.attn = LlamaAttention(hidden, num_heads, rope_theta=rope_theta)
+        self.attn = LlamaAttention(hidden, num_heads, num_kv_heads,
+                                   rope_theta=rope_theta)
         self.rms2 = FusedRMSNorm(hidden, eps=eps)
         # gate and up projections as ONE GEMM: columns [0, F) gate, [F, 2F) up
         self.fc12 = nn.Linear(hidden, 2 * ffn_hidden, bias=False)
@@ -111,11 +133,12 @@ class LlamaHead(nn.Module):
 
 class LlamaCore(nn.Module):
     def __init__(self, layers, hidden, heads, ffn, vocab_size,
-                 rope_theta=10000.0):
+                 rope_theta=10000.0, kv_heads=None):
         super().__init__()
         self.embeddings = LlamaEmbedding(vocab_size, hidden)
         self.blocks = nn.ModuleList(
-            LlamaBlock(hidden, heads, ffn, rope_theta=rope_theta)
+            LlamaBlock(hidden, heads, ffn, rope_theta=rope_theta,
+                       num_kv_heads=kv_heads)
             for _ in range(layers))
         self.head = LlamaHead(hidden, vocab_size)
 
@@ -134,9 +157,11 @@ def build_llama(config="llama-7b", vocab_size=32000, max_pos=2048,
     sequence length they meet."""
     cfg = LLAMA_CONFIGS[config] if isinstance(config, str) else dict(config)
     L, H, A, F = cfg["layers"], cfg["hidden"], cfg["heads"], cfg["ffn"]
+    KV = cfg.get("kv_heads")
     if num_stages <= 1:
         with epl.replicate(device_count=1, name="stage_0"):
-            model = LlamaCore(L, H, A, F, vocab_size, rope_theta=rope_theta)
+            model = LlamaCore(L, H, A, F, vocab_size, rope_theta=rope_theta,
+                              kv_heads=KV)
         model.max_pos = max_pos
         return init_weights(model)
     per = (L + num_stages - 1) // num_stages
@@ -148,7 +173,8 @@ def build_llama(config="llama-7b", vocab_size=32000, max_pos=2048,
             if s == 0:
                 mods.append(LlamaEmbedding(vocab_size, H))
             n = min(per, L - layer_idx)
-            mods.extend(LlamaBlock(H, A, F, rope_theta=rope_theta)
+            mods.extend(LlamaBlock(H, A, F, rope_theta=rope_theta,
+                                   num_kv_heads=KV)
                         for _ in range(n))
             layer_idx += n
             if s == num_stages - 1:

@@ -16,6 +16,14 @@ the length of out and of every gradient are exact zeros, and nothing at
 a valid position depends on what the padding holds.  The kernels read
 and clamp the lengths themselves (no host sync), skip the padded tiles
 and exit whole blocks past the length.
+
+Grouped-query attention: ``flash_attention`` takes k and v with Hkv heads
+where Hkv divides the H heads of q; query head h attends kv head
+h // (H // Hkv), the ``repeat_interleave`` order.  The GQA kernels read
+K / V where they are and sum dk / dv over a group's heads in registers:
+nothing is expanded and the gradients come back in the kv shape.  They
+have no dropout: a GQA call with dropout_p > 0 (like fp32 and the CPU)
+expands k and v and takes the torch path, where autograd does the sum.
 """
 
 import os
@@ -163,6 +171,50 @@ class _FlashAttention(torch.autograd.Function):
                               ctx.scale, ctx.causal, _bwd_split(), mask,
                               ctx.inv_keep, None, seqlens)
         return dq, dk, dv, None, None, None, None
+
+
+class _FlashAttentionGQA(torch.autograd.Function):
+    """Grouped-query flash attention: q [B, H, S, D], k / v [B, Hkv, S, D]
+    (any kernel-ok strides, k and v sharing theirs).  dk and dv are
+    allocated and written in the kv shape."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, seqlens=None):
+        if not _kernel_ok(q):
+            q = q.contiguous()
+        if not (_kernel_ok(k) and _kernel_ok(v)
+                and k.stride() == v.stride()):
+            k, v = k.contiguous(), v.contiguous()
+        b, h, seq, d = q.shape
+        out = torch.empty(b, seq, h, d, dtype=q.dtype,
+                          device=q.device).permute(0, 2, 1, 3)
+        lse = torch.empty(b * h * seq, dtype=torch.float32,
+                          device=q.device)
+        native_ext().attn_fwd_gqa(q, k, v, out, lse, scale, causal, seqlens)
+        ctx.has_seqlens = seqlens is not None
+        ctx.save_for_backward(q, k, v, out, lse, *[
+            t for t in (seqlens,) if t is not None])
+        ctx.causal = causal
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
+        q, k, v, out, lse = saved[:5]
+        seqlens = saved[5] if ctx.has_seqlens else None
+        if not _kernel_ok(dout):
+            dout = dout.contiguous()
+        dq = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype,
+                                 device=q.device)
+        dk = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype,
+                                 device=k.device)
+        dv = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype,
+                                 device=k.device)
+        delta = torch.empty_like(lse)
+        native_ext().attn_bwd_gqa(q, k, v, out, dout, lse, delta, dq, dk,
+                                  dv, ctx.scale, ctx.causal, seqlens)
+        return dq, dk, dv, None, None, None
 
 
 class _QKVFlashAttention(torch.autograd.Function):
@@ -326,19 +378,37 @@ def qkv_native_ok(qkv):
 
 def flash_attention(q, k, v, causal=False, scale=None, allow_native=True,
                     dropout_p=0.0, seqlens=None):
-    """q,k,v: [B, H, S, D].  Native kernel when bf16/D=64 on GPU; torch
-    SDPA otherwise.  dropout_p runs in-kernel on the native path
-    (training-mode callers only).  seqlens: int32 [B] valid lengths of a
-    right-padded batch (module docstring); the fallback keeps the same
-    semantics."""
+    """q: [B, H, S, D]; k, v: [B, Hkv, S, D] with Hkv dividing H (grouped
+    -query attention when Hkv < H, module docstring).  Native kernel when
+    bf16/D=64|128 on GPU; torch SDPA otherwise.  dropout_p runs in-kernel
+    on the native path (training-mode callers only; not with GQA).
+    seqlens: int32 [B] valid lengths of a right-padded batch (module
+    docstring); the fallback keeps the same semantics."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     seqlens = _check_seqlens(seqlens, q)
+    heads, kv_heads = q.shape[1], k.shape[1]
+    if kv_heads != heads and (v.shape[1] != kv_heads or kv_heads < 1
+                              or heads % kv_heads):
+        raise ValueError(
+            "k and v must share a head count that divides q's {}, got {} "
+            "and {}".format(heads, kv_heads, v.shape[1]))
     if allow_native and use_native(q):
         if q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
-            return _FlashAttention.apply(q, k, v, causal, scale, dropout_p,
-                                         seqlens)
-        _warn_fallback("dtype={} head_dim={}".format(q.dtype, q.shape[-1]))
+            if kv_heads == heads:
+                return _FlashAttention.apply(q, k, v, causal, scale,
+                                             dropout_p, seqlens)
+            if not dropout_p:
+                return _FlashAttentionGQA.apply(q, k, v, causal, scale,
+                                                seqlens)
+            _warn_fallback("grouped-query attention with dropout")
+        else:
+            _warn_fallback("dtype={} head_dim={}".format(q.dtype,
+                                                         q.shape[-1]))
+    if kv_heads != heads:
+        # autograd sums the expanded gradients over each group
+        k = k.repeat_interleave(heads // kv_heads, dim=1)
+        v = v.repeat_interleave(heads // kv_heads, dim=1)
     if seqlens is not None:
         return _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens)
     return F.scaled_dot_product_attention(q, k, v, is_causal=causal,

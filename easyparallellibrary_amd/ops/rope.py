@@ -7,7 +7,8 @@ convention: element i < D/2 of a head pairs with element i + D/2,
 The HIP kernel (csrc/kernels/llama_ops.hip: rope_kernel) rotates a strided
 [B, S, N, D] bf16 view IN PLACE, D in (64, 128): the q and k slices of the
 packed [B, S, 3, H, D] projection buffer as N = 2H heads (v is never
-touched), or a stand-alone q / k.  Its ``inverse`` flag applies the
+touched; grouped-query: the first N = H + Hkv heads of [B, S, H + 2 Hkv,
+D]), or a stand-alone q / k.  Its ``inverse`` flag applies the
 transposed rotation, which is the backward.  There is no on-device
 trigonometry: cos / sin come from fp32 [L, D/2] tables computed in fp64 on
 the host and rounded once.
@@ -104,40 +105,54 @@ def apply_rope(x, pos0=0, theta=10000.0):
 
 class _RopeQKVFlashAttention(torch.autograd.Function):
     """RoPE + flash attention on the packed projection output
-    [B, S, 3*H*D], no full-size copy in either direction.
+    [B, S, (H + 2 Hkv) * D] (q heads, then k heads, then v heads; Hkv = H
+    is the [B, S, 3*H*D] MHA buffer), no full-size copy in either
+    direction.
 
-    Forward rotates the q and k slices IN PLACE (the input is marked dirty
-    and returned as the second output, as autograd's in-place rules ask)
-    and runs attn_fwd on the strided views; the saved buffer is the rotated
-    one, which is what attn_bwd needs.  Backward lets attn_bwd write into
-    the slices of its own fresh d_qkv, rotates the dq / dk slices back in
-    place and returns it."""
+    Forward rotates the q and k heads IN PLACE, the first H + Hkv heads of
+    the [B, S, H + 2 Hkv, D] view (the input is marked dirty and returned
+    as the second output, as autograd's in-place rules ask) and runs the
+    attention forward on the strided slices; the saved buffer is the
+    rotated one, which is what the backward needs.  Backward lets the
+    attention backward write into the slices of its own fresh d_qkv,
+    rotates the dq / dk heads back in place and returns it."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, causal, scale, dropout_p, seqlens, cos, sin,
-                pos0):
+    def _slices(buf, heads, kv_heads):
+        """q [B, H, S, D], k and v [B, Hkv, S, D] views of the packed
+        [B, S, H + 2 Hkv, D] buffer"""
+        return (buf[:, :, :heads].transpose(1, 2),
+                buf[:, :, heads:heads + kv_heads].transpose(1, 2),
+                buf[:, :, heads + kv_heads:].transpose(1, 2))
+
+    @staticmethod
+    def forward(ctx, qkv, heads, kv_heads, causal, scale, dropout_p,
+                seqlens, cos, sin, pos0):
         b, s, width = qkv.shape
-        d = width // (3 * heads)
+        d = width // (heads + 2 * kv_heads)
         ctx.mark_dirty(qkv)
-        packed = qkv.view(b, s, 3, heads, d)
-        native_ext().rope_(packed[:, :, :2].view(b, s, 2 * heads, d), cos,
-                           sin, pos0, False)
-        q = packed[:, :, 0].transpose(1, 2)
-        k = packed[:, :, 1].transpose(1, 2)
-        v = packed[:, :, 2].transpose(1, 2)
+        packed = qkv.view(b, s, heads + 2 * kv_heads, d)
+        native_ext().rope_(packed[:, :, :heads + kv_heads], cos, sin, pos0,
+                           False)
+        q, k, v = _RopeQKVFlashAttention._slices(packed, heads, kv_heads)
         out = torch.empty(b, s, heads, d, dtype=qkv.dtype,
                           device=qkv.device).permute(0, 2, 1, 3)
         lse = torch.empty(b * heads * s, dtype=torch.float32,
                           device=qkv.device)
         thresh, inv_keep, seed = _drop_params(dropout_p)
         mask = _mask_tensor(b, heads, s, qkv.device) if thresh else None
-        native_ext().attn_fwd(q, k, v, out, lse, scale, causal, mask, seed,
-                              thresh, inv_keep, seqlens)
+        if kv_heads == heads:
+            native_ext().attn_fwd(q, k, v, out, lse, scale, causal, mask,
+                                  seed, thresh, inv_keep, seqlens)
+        else:
+            native_ext().attn_fwd_gqa(q, k, v, out, lse, scale, causal,
+                                      seqlens)
         ctx.has_mask = mask is not None
         ctx.has_seqlens = seqlens is not None
         ctx.save_for_backward(qkv, out, lse, cos, sin, *[
             t for t in (mask, seqlens) if t is not None])
-        ctx.heads, ctx.causal, ctx.scale = heads, causal, scale
+        ctx.heads, ctx.kv_heads = heads, kv_heads
+        ctx.causal, ctx.scale = causal, scale
         ctx.inv_keep, ctx.pos0 = inv_keep, pos0
         ctx.set_materialize_grads(False)
         return out, qkv
@@ -148,45 +163,51 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
         qkv, out, lse, cos, sin = saved[:5]
         mask, seqlens = _saved_optionals(ctx, saved[5:])
         b, s, width = qkv.shape
-        heads = ctx.heads
-        d = width // (3 * heads)
+        heads, kv_heads = ctx.heads, ctx.kv_heads
+        d = width // (heads + 2 * kv_heads)
         dqkv = torch.empty_like(qkv)
-        dpacked = dqkv.view(b, s, 3, heads, d)
+        dpacked = dqkv.view(b, s, heads + 2 * kv_heads, d)
         if dout is None:
             dqkv.zero_()
         else:
-            packed = qkv.view(b, s, 3, heads, d)
-            q = packed[:, :, 0].transpose(1, 2)
-            k = packed[:, :, 1].transpose(1, 2)
-            v = packed[:, :, 2].transpose(1, 2)
+            q, k, v = _RopeQKVFlashAttention._slices(
+                qkv.view(b, s, heads + 2 * kv_heads, d), heads, kv_heads)
             if not _kernel_ok(dout):
                 dout = dout.contiguous()
-            dq = dpacked[:, :, 0].transpose(1, 2)
-            dk = dpacked[:, :, 1].transpose(1, 2)
-            dv = dpacked[:, :, 2].transpose(1, 2)
+            dq, dk, dv = _RopeQKVFlashAttention._slices(dpacked, heads,
+                                                        kv_heads)
             delta = torch.empty_like(lse)
-            native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv,
-                                  ctx.scale, ctx.causal, True, mask,
-                                  ctx.inv_keep, None, seqlens)
+            if kv_heads == heads:
+                native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk,
+                                      dv, ctx.scale, ctx.causal, True, mask,
+                                      ctx.inv_keep, None, seqlens)
+            else:
+                native_ext().attn_bwd_gqa(q, k, v, out, dout, lse, delta, dq,
+                                          dk, dv, ctx.scale, ctx.causal,
+                                          seqlens)
         if drot is not None:
             # a consumer of the rotated buffer itself: its gradient is in
             # the rotated frame too, so it joins before the rotation back
             dqkv += drot
-        native_ext().rope_(dpacked[:, :, :2].view(b, s, 2 * heads, d), cos,
-                           sin, ctx.pos0, True)
-        return dqkv, None, None, None, None, None, None, None, None
+        native_ext().rope_(dpacked[:, :, :heads + kv_heads], cos, sin,
+                           ctx.pos0, True)
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
-def rope_qkv_native_ok(qkv, heads):
+def rope_qkv_native_ok(qkv, heads, kv_heads=None):
     """shapes _RopeQKVFlashAttention takes: the contiguous bf16 [B, S,
-    3*H*D] projection output (or its [B, S, 3, H, D] view) with
-    D in (64, 128)"""
-    if qkv.dim() == 5:
-        if qkv.shape[2] != 3 or qkv.shape[3] != heads:
-            return False
-    elif qkv.dim() != 3 or qkv.shape[-1] % (3 * heads):
+    (H + 2*Hkv)*D] projection output (Hkv = H by default: [B, S, 3*H*D],
+    or its [B, S, 3, H, D] view) with D in (64, 128)"""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads < 1 or heads % kv_heads:
         return False
-    d = qkv.shape[-1] if qkv.dim() == 5 else qkv.shape[-1] // (3 * heads)
+    units = heads + 2 * kv_heads
+    if qkv.dim() == 5:
+        if qkv.shape[2] != 3 or qkv.shape[3] != heads or kv_heads != heads:
+            return False
+    elif qkv.dim() != 3 or qkv.shape[-1] % units:
+        return False
+    d = qkv.shape[-1] if qkv.dim() == 5 else qkv.shape[-1] // units
     return (use_native(qkv) and qkv.dtype == torch.bfloat16
             and d in (64, 128) and qkv.is_contiguous() and qkv.numel() > 0
             and qkv.data_ptr() % 16 == 0)
@@ -194,7 +215,7 @@ def rope_qkv_native_ok(qkv, heads):
 
 def rope_qkv_flash_attention(qkv, causal=True, dropout_p=0.0, seqlens=None,
                              pos0=0, theta=10000.0, scale=None,
-                             num_heads=None):
+                             num_heads=None, num_kv_heads=None):
     """Rotary embedding of q and k, then flash attention, on the packed
     projection output.  Native kernels only (rope_qkv_native_ok); callers
     use apply_rope + flash_attention otherwise.
@@ -208,6 +229,10 @@ def rope_qkv_flash_attention(qkv, causal=True, dropout_p=0.0, seqlens=None,
     copy in backward, and forbids one on such a leaf, so the copy is made
     once, in the forward only.  The kernel stays in place either way.
 
+    Grouped-query attention: ``num_kv_heads`` = Hkv < H takes the packed
+    [B, S, (H + 2*Hkv)*D] output — H query heads, then Hkv key heads, then
+    Hkv value heads — in the same zero-copy way (no dropout).
+
     Returns the attention output as a [B, H, S, D] view whose memory order
     is [B, S, H, D].  dropout_p, seqlens: as qkv_flash_attention.  pos0:
     position of the first token."""
@@ -215,24 +240,32 @@ def rope_qkv_flash_attention(qkv, causal=True, dropout_p=0.0, seqlens=None,
         b, s, _, heads, d = qkv.shape
         if num_heads is not None and num_heads != heads:
             raise ValueError("num_heads does not match qkv")
+        if num_kv_heads not in (None, heads):
+            raise ValueError("a 5-D qkv has equal q and kv head counts")
+        kv_heads = heads
         # the 3-D form of a 5-D tensor is a view of it: always the copy
         flat = qkv.reshape(b, s, 3 * heads * d).clone()
     else:
         if num_heads is None:
             raise ValueError("a [B, S, 3*H*D] qkv needs num_heads")
         b, s, width = qkv.shape
-        heads, d = num_heads, width // (3 * num_heads)
+        heads = num_heads
+        kv_heads = heads if num_kv_heads is None else num_kv_heads
+        d = width // (heads + 2 * kv_heads)
         flat = qkv
         if flat._is_view() or (flat.is_leaf and flat.requires_grad):
             flat = flat.clone()
-    if not rope_qkv_native_ok(flat, heads):
+    if not rope_qkv_native_ok(flat, heads, kv_heads):
         raise ValueError(
             "rope_qkv_flash_attention needs the native kernels: contiguous "
             "bf16 qkv on the GPU with head_dim 64 or 128")
+    if kv_heads != heads and dropout_p:
+        raise ValueError("the grouped-query kernels have no dropout")
     if scale is None:
         scale = d ** -0.5
     seqlens = _check_seqlens(seqlens, flat)
     cos, sin = rope_tables(flat.device, d, theta, pos0 + s)
-    out, _ = _RopeQKVFlashAttention.apply(flat, heads, causal, scale,
-                                          dropout_p, seqlens, cos, sin, pos0)
+    out, _ = _RopeQKVFlashAttention.apply(flat, heads, kv_heads, causal,
+                                          scale, dropout_p, seqlens, cos,
+                                          sin, pos0)
     return out

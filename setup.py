@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/kernels/moe_router.hip",
         "csrc/kernels/mfma_probe.hip",
         "csrc/kernels/attention.hip",
+        "csrc/kernels/attention_gqa.hip",
     ],
     include_dirs=[os.path.join(ROCM, "include")],
     library_dirs=[os.path.join(ROCM, "lib")],
