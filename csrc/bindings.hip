@@ -102,6 +102,12 @@ void epl_rope(void*, const float*, const float*, int64_t, int64_t, int64_t,
 void epl_swiglu_fwd(void*, const void*, int64_t, int64_t, hipStream_t);
 void epl_swiglu_bwd(void*, const void*, const void*, int64_t, int64_t,
                     hipStream_t);
+void epl_rows_live_index(int*, int*, int*, const void*, int64_t, int64_t,
+                         bool, hipStream_t);
+void epl_gather_rows(void*, const void*, const int*, const int*, int64_t,
+                     int64_t, int64_t, hipStream_t);
+void epl_scatter_rows_zero(void*, const void*, const int*, int64_t, int64_t,
+                           int64_t, hipStream_t);
 }
 
 namespace {
@@ -1102,6 +1108,94 @@ void swiglu_bwd(at::Tensor dgu, at::Tensor dy, at::Tensor gu) {
                  cur_stream());
 }
 
+// ---- live rows of a [N, C] matrix (csrc/kernels/kernels.hip) ---------------
+// Nothing is read on the host: count stays a device tensor.
+
+// a contiguous 2-D bf16 / fp32 device matrix whose rows are whole 16-byte
+// pieces from a 16-byte-aligned base; returns the bytes of a row
+static int64_t live_rows_matrix(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 2, name,
+              " must be a contiguous 2-D device tensor");
+  is_bf16(t);
+  TORCH_CHECK(t.size(0) >= 1 && t.size(0) < (int64_t(1) << 31) &&
+                  t.size(1) >= 1,
+              name, " needs 1 <= rows < 2^31 and a column");
+  const int64_t row_bytes = t.size(1) * (int64_t)t.element_size();
+  TORCH_CHECK(row_bytes % 16 == 0, name, ": a row must be a multiple of 16 "
+              "bytes, got ", row_bytes);
+  TORCH_CHECK(aligned16(t), name, " must be 16-byte aligned");
+  return row_bytes;
+}
+
+static void live_rows_map(const at::Tensor& t, const at::Tensor& like,
+                          int64_t numel, const char* name) {
+  check(t, at::kInt, name);
+  TORCH_CHECK(t.device() == like.device(), name, " is on another device");
+  TORCH_CHECK(t.numel() == numel, name, " must hold ", numel, " elements");
+}
+
+// (idx int32 [N], count int32 [1], inv int32 [N]): a row of g is live if any
+// element compares != 0 (-0.0 is zero, a NaN is not).  idx[0:count] are the
+// live rows in ascending order, idx[count:] = -1; inv[r] is r's position in
+// idx, -1 for a dead row.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> rows_live_index(at::Tensor g) {
+  const int64_t row_bytes = live_rows_matrix(g, "g");
+  const int64_t n = g.size(0);
+  const auto opts = g.options().dtype(at::kInt);
+  at::Tensor idx = at::empty({n}, opts);
+  at::Tensor inv = at::empty({n}, opts);
+  at::Tensor count = at::empty({1}, opts);
+  epl_rows_live_index(idx.data_ptr<int>(), inv.data_ptr<int>(),
+                      count.data_ptr<int>(), g.data_ptr(), n, row_bytes,
+                      is_bf16(g), cur_stream());
+  return std::make_tuple(idx, count, inv);
+}
+
+// the output of a gather / scatter: ``out`` when given (rows x src's columns,
+// src's dtype, contiguous), else a fresh tensor
+static at::Tensor live_rows_out(const c10::optional<at::Tensor>& out,
+                                const at::Tensor& src, int64_t rows) {
+  at::Tensor o = out.has_value()
+                     ? *out
+                     : at::empty({rows, src.size(1)}, src.options());
+  check(o, src.scalar_type(), "out");
+  TORCH_CHECK(o.device() == src.device(), "out is on another device");
+  TORCH_CHECK(o.dim() == 2 && o.size(0) == rows && o.size(1) == src.size(1),
+              "out must be [", rows, ", ", src.size(1), "]");
+  TORCH_CHECK(aligned16(o), "out must be 16-byte aligned");
+  return o;
+}
+
+// out [n_pad, C]: out[p] = src[idx[p]] for p < count, zero rows after
+at::Tensor gather_rows(at::Tensor src, at::Tensor idx, at::Tensor count,
+                       int64_t n_pad, c10::optional<at::Tensor> out) {
+  const int64_t row_bytes = live_rows_matrix(src, "src");
+  live_rows_map(idx, src, src.size(0), "idx");
+  live_rows_map(count, src, 1, "count");
+  TORCH_CHECK(n_pad >= 1 && n_pad < (int64_t(1) << 31),
+              "gather_rows: 1 <= n_pad < 2^31, got ", n_pad);
+  at::Tensor o = live_rows_out(out, src, n_pad);
+  epl_gather_rows(o.data_ptr(), src.data_ptr(), idx.data_ptr<int>(),
+                  count.data_ptr<int>(), src.size(0), n_pad, row_bytes,
+                  cur_stream());
+  return o;
+}
+
+// out [N, C], N = inv.numel(): out[r] = src[inv[r]] for a live r, a zero
+// row for inv[r] < 0 (or past src).  Every row of out is written.
+at::Tensor scatter_rows_zero(at::Tensor src, at::Tensor inv,
+                             c10::optional<at::Tensor> out) {
+  const int64_t row_bytes = live_rows_matrix(src, "src");
+  const int64_t n = inv.numel();
+  TORCH_CHECK(n >= 1 && n < (int64_t(1) << 31),
+              "scatter_rows_zero: 1 <= rows < 2^31, got ", n);
+  live_rows_map(inv, src, n, "inv");
+  at::Tensor o = live_rows_out(out, src, n);
+  epl_scatter_rows_zero(o.data_ptr(), src.data_ptr(), inv.data_ptr<int>(),
+                        n, src.size(0), row_bytes, cur_stream());
+  return o;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1176,4 +1270,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pos0"), py::arg("inverse"));
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
+  m.def("rows_live_index", &rows_live_index, py::arg("g"));
+  m.def("gather_rows", &gather_rows, py::arg("src"), py::arg("idx"),
+        py::arg("count"), py::arg("n_pad"), py::arg("out") = py::none());
+  m.def("scatter_rows_zero", &scatter_rows_zero, py::arg("src"),
+        py::arg("inv"), py::arg("out") = py::none());
 }

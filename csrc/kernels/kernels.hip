@@ -1177,6 +1177,145 @@ __global__ void sqnorm_kernel(const void* __restrict__ p, int64_t n,
   if (threadIdx.x == 0) atomicAdd(out, acc);
 }
 
+// ============================================================================
+// Live rows of a [N, C] matrix: index, gather, scatter.
+// The MLM head's upstream gradient has exactly-zero rows wherever the target
+// is ignored (85 % of them); its backward GEMMs run on the live rows only.
+//   rows_flag_kernel    inv[r] = 1 if row r holds an element != 0, else 0
+//   rows_scan_kernel    one block: idx[0:count] = live rows ascending,
+//                       idx[count:N] = -1, inv[r] = position of r in idx or
+//                       -1, count[0] = count.  Placement is a prefix sum in
+//                       row order: no atomics, equal bits on every run.
+//   gather_rows_kernel  out[p] = src[idx[p]] for p < count, zeros for the
+//                       pad rows count <= p < n_pad
+//   scatter_rows_zero_kernel  out[r] = src[inv[r]] for live r, zeros else
+// Rows are moved as 16-byte pieces whatever the element type (row bytes
+// % 16 == 0, checked by the binding): a wave owns a row, a load instruction
+// covers 1 KiB of it (eight lanes per 128-byte line).  Every output row is
+// written exactly once with plain vector stores; count stays on the device.
+// ============================================================================
+constexpr int kLiveUnroll = 4;      // 16-byte loads in flight per lane
+constexpr int kScanThreads = 1024;
+
+// MASK drops the sign bits: x != 0 as a floating-point value (so -0.0 is
+// zero and a NaN is not) is (bits & MASK) != 0.  0x7fff7fff: two bf16 per
+// word; 0x7fffffff: fp32.
+template <unsigned MASK>
+__global__ __launch_bounds__(256) void rows_flag_kernel(
+    int* __restrict__ inv, const uint4* __restrict__ g, int64_t rows,
+    int64_t row_vecs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t row = wave; row < rows; row += nwaves) {
+    const uint4* p = g + row * row_vecs;
+    bool live = false;
+    // a live row stops at the first piece that shows it; a dead row is
+    // read to its end
+    for (int64_t c0 = 0; c0 < row_vecs && !live; c0 += 64 * kLiveUnroll) {
+      unsigned acc = 0;
+#pragma unroll
+      for (int k = 0; k < kLiveUnroll; ++k) {
+        const int64_t c = c0 + k * 64 + lane;
+        if (c < row_vecs) {
+          const uint4 v = p[c];
+          acc |= v.x | v.y | v.z | v.w;
+        }
+      }
+      live = __any((acc & MASK) != 0);
+    }
+    if (lane == 0) inv[row] = live ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void rows_scan_kernel(
+    int* __restrict__ idx, int* __restrict__ inv, int* __restrict__ count,
+    int64_t rows) {
+  __shared__ int wave_tot[kScanThreads / 64];
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  // thread t owns the rows [r0, r1): ascending in t, so ascending in idx
+  const int64_t per = (rows + kScanThreads - 1) / kScanThreads;
+  const int64_t r0 = (int64_t)t * per < rows ? (int64_t)t * per : rows;
+  const int64_t r1 = r0 + per < rows ? r0 + per : rows;
+  int mine = 0;
+  for (int64_t r = r0; r < r1; ++r) mine += inv[r];
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kScanThreads / 64; ++w) {
+    const int v = wave_tot[w];
+    if (w < wave) before += v;
+    total += v;
+  }
+  int pos = before + incl - mine;
+  for (int64_t r = r0; r < r1; ++r) {
+    if (inv[r] != 0) {
+      idx[pos] = (int)r;
+      inv[r] = pos++;
+    } else {
+      inv[r] = -1;
+    }
+  }
+  for (int64_t i = total + t; i < rows; i += kScanThreads) idx[i] = -1;
+  if (t == 0) count[0] = total;
+}
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(
+    uint4* __restrict__ out, const uint4* __restrict__ src,
+    const int* __restrict__ idx, const int* __restrict__ count,
+    int64_t src_rows, int64_t n_pad, int64_t row_vecs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t n_live = count[0];
+  for (int64_t p = wave; p < n_pad; p += nwaves) {
+    // idx holds src_rows entries; anything that is not a row of src gives
+    // a zero row rather than a read outside it
+    int64_t s = (p < n_live && p < src_rows) ? idx[p] : -1;
+    if (s >= src_rows) s = -1;
+    uint4* o = out + p * row_vecs;
+    if (s >= 0) {
+      const uint4* in = src + s * row_vecs;
+      for (int64_t c = lane; c < row_vecs; c += 64) o[c] = in[c];
+    } else {
+      for (int64_t c = lane; c < row_vecs; c += 64)
+        o[c] = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void scatter_rows_zero_kernel(
+    uint4* __restrict__ out, const uint4* __restrict__ src,
+    const int* __restrict__ inv, int64_t rows, int64_t src_rows,
+    int64_t row_vecs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = __builtin_amdgcn_readfirstlane(
+      (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t r = wave; r < rows; r += nwaves) {
+    int64_t s = inv[r];
+    if (s >= src_rows) s = -1;
+    uint4* o = out + r * row_vecs;
+    if (s >= 0) {
+      const uint4* in = src + s * row_vecs;
+      for (int64_t c = lane; c < row_vecs; c += 64) o[c] = in[c];
+    } else {
+      for (int64_t c = lane; c < row_vecs; c += 64)
+        o[c] = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
+
 }  // namespace
 
 // ============================================================================
@@ -1611,6 +1750,47 @@ void epl_colsum(void* db, const void* dy, float* partial, int64_t rows,
   else
     hipLaunchKernelGGL((colsum_reduce_kernel<false>), rgrid, dim3(256), 0,
                        stream, db, partial, stripes, cols);
+}
+
+// blocks of four waves, a wave per row, capped: the waves stride the rows
+static int live_rows_grid(int64_t rows) {
+  const int64_t blocks = (rows + 3) / 4;
+  return (int)(blocks < 1 ? 1 : (blocks < 8192 ? blocks : 8192));
+}
+
+// g: [rows, row_bytes / 16] 16-byte pieces; idx, inv: int32 [rows];
+// count: int32 [1].  rows >= 1.
+void epl_rows_live_index(int* idx, int* inv, int* count, const void* g,
+                         int64_t rows, int64_t row_bytes, bool bf16,
+                         hipStream_t stream) {
+  const int grid = live_rows_grid(rows);
+  const uint4* gp = reinterpret_cast<const uint4*>(g);
+  if (bf16)
+    hipLaunchKernelGGL(rows_flag_kernel<0x7fff7fffu>, dim3(grid), dim3(256),
+                       0, stream, inv, gp, rows, row_bytes / 16);
+  else
+    hipLaunchKernelGGL(rows_flag_kernel<0x7fffffffu>, dim3(grid), dim3(256),
+                       0, stream, inv, gp, rows, row_bytes / 16);
+  hipLaunchKernelGGL(rows_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream,
+                     idx, inv, count, rows);
+}
+
+void epl_gather_rows(void* out, const void* src, const int* idx,
+                     const int* count, int64_t src_rows, int64_t n_pad,
+                     int64_t row_bytes, hipStream_t stream) {
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(live_rows_grid(n_pad)),
+                     dim3(256), 0, stream, reinterpret_cast<uint4*>(out),
+                     reinterpret_cast<const uint4*>(src), idx, count,
+                     src_rows, n_pad, row_bytes / 16);
+}
+
+void epl_scatter_rows_zero(void* out, const void* src, const int* inv,
+                           int64_t rows, int64_t src_rows, int64_t row_bytes,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_rows_zero_kernel, dim3(live_rows_grid(rows)),
+                     dim3(256), 0, stream, reinterpret_cast<uint4*>(out),
+                     reinterpret_cast<const uint4*>(src), inv, rows, src_rows,
+                     row_bytes / 16);
 }
 
 }  // extern "C"

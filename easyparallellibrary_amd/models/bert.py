@@ -32,10 +32,13 @@ class BertCore(nn.Module):
     padding: valid positions neither see the padding nor pay for it.
     ``forward(ids, seqlens=...)`` takes explicit int32 [B] lengths
     instead.  Logits at padded positions are meaningless; give them the
-    target -100."""
+    target -100.
+
+    live_rows_bwd: see LMHead; build_bert turns it on (an MLM loss
+    ignores most positions)."""
 
     def __init__(self, layers, hidden, heads, ffn, vocab_size, max_pos,
-                 dropout=0.0, pad_token_id=None):
+                 dropout=0.0, pad_token_id=None, live_rows_bwd=False):
         super().__init__()
         self.pad_token_id = pad_token_id
         self.embeddings = Embeddings(vocab_size, hidden, max_pos)
@@ -43,7 +46,7 @@ class BertCore(nn.Module):
             Block(hidden, heads, ffn, causal=False, pre_ln=False,
                   dropout=dropout)
             for _ in range(layers))
-        self.head = LMHead(hidden, vocab_size)
+        self.head = LMHead(hidden, vocab_size, live_rows_bwd=live_rows_bwd)
 
     def forward(self, ids, seqlens=None):
         if seqlens is None and self.pad_token_id is not None:
@@ -107,7 +110,8 @@ def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
     if num_stages <= 1:
         with epl.replicate(device_count=1, name="stage_0"):
             model = BertCore(L, H, A, F, vocab_size, max_pos,
-                             dropout=dropout, pad_token_id=pad_token_id)
+                             dropout=dropout, pad_token_id=pad_token_id,
+                             live_rows_bwd=True)
         return init_weights(model)
     if pad_token_id is not None:
         raise ValueError(
@@ -127,7 +131,7 @@ def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
                         for _ in range(n))
             layer_idx += n
             if s == num_stages - 1:
-                mods.append(LMHead(H, vocab_size))
+                mods.append(LMHead(H, vocab_size, live_rows_bwd=True))
             stages.append(_Stage(mods))
     return init_weights(StagedModel(stages))
 

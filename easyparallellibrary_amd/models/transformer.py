@@ -27,6 +27,8 @@ from easyparallellibrary_amd.ops.bias_gelu import FusedBiasGelu
 from easyparallellibrary_amd.ops.bias_linear import FusedBiasLinear
 from easyparallellibrary_amd.ops.layer_norm import (FusedLayerNorm,
                                                     linear_for_ln)
+from easyparallellibrary_amd.ops.lm_head import (LiveRowsLinear,
+                                                 resolve_live_rows)
 
 # Linear bias grads via the fused colsum kernel.  The kernel wins per-op
 # (vs torch's ~2.2 TB/s reduce) but the path loses end-to-end: r1 592 vs
@@ -217,17 +219,31 @@ class Embeddings(nn.Module):
 
 
 class LMHead(nn.Module):
-    """Projection to vocab logits (untied for simplicity)."""
+    """Projection to vocab logits (untied for simplicity).
 
-    def __init__(self, hidden, vocab_size, use_ln=True):
+    live_rows_bwd: the projection's backward runs its two GEMMs on the
+    rows of the incoming gradient that are not entirely zero
+    (ops/lm_head.py).  For heads under a loss that ignores most positions
+    (MLM: build_bert turns it on); it costs one host sync per backward, so
+    heads with every row live, or inside a captured graph, leave it off.
+    The logits are the same either way.  EPL_LMHEAD_LIVE_ROWS=0/1 forces
+    it for every head."""
+
+    def __init__(self, hidden, vocab_size, use_ln=True, live_rows_bwd=False):
         super().__init__()
         self.ln = FusedLayerNorm(hidden) if use_ln else None
         self.proj = nn.Linear(hidden, vocab_size, bias=False)
+        self.live_rows_bwd = resolve_live_rows(live_rows_bwd)
         nn.init.normal_(self.proj.weight, std=0.02)
 
     def forward(self, x):
         if self.ln is not None:
             x = self.ln(x)
+        # x.dtype == weight.dtype: under AMP-O1 (bf16 activations over fp32
+        # weights) autocast's own F.linear keeps the GEMM dtypes straight
+        if self.live_rows_bwd and type(self.proj) is nn.Linear \
+                and x.dtype == self.proj.weight.dtype:
+            return LiveRowsLinear.apply(x, self.proj.weight)
         return self.proj(x)
 
 
