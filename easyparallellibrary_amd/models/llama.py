@@ -15,6 +15,14 @@ modules): one packed projection of H query, Hkv key and Hkv value heads;
 the GQA flash kernels read K / V once per group and sum dK / dV over the
 group in registers (docs/kernels.md), nothing is expanded.
 
+Packed documents and sliding windows: ``LlamaCore.forward(ids,
+segment_ids)`` keeps every token's attention inside its own document (a
+maximal run of equal consecutive ids in a row), and a config's ``window``
+(``mistral-7b``) limits it to the last ``window`` keys; both run the banded
+causal flash kernels (ops/attention.py).  RoPE positions keep counting
+along the row and do not restart per document.  The per-row bounds are
+computed once per forward in LlamaCore and shared by all layers.
+
 Out of scope: tensor-parallel sharding of the packed qkv and gate/up
 weights, KV-cache decoding, and a bench.py config.
 """
@@ -39,6 +47,11 @@ LLAMA_CONFIGS = {
     # rope_theta=500000.0 and vocab_size=128256
     "llama3-8b": dict(layers=32, hidden=4096, heads=32, kv_heads=8,
                       ffn=14336),
+    # Mistral-7B: GQA with a 4096-key sliding window
+    "mistral-7b": dict(layers=32, hidden=4096, heads=32, kv_heads=8,
+                       ffn=14336, window=4096),
+    "llama-tiny-swa": dict(layers=2, hidden=128, heads=2, kv_heads=1,
+                           ffn=352, window=48),
 }
 
 
@@ -46,10 +59,11 @@ class LlamaAttention(nn.Module):
     """Causal self-attention with rotary q / k; bias-free projections.
     ``num_kv_heads`` < ``num_heads`` is grouped-query attention: the one
     packed projection emits H query, Hkv key and Hkv value heads, and
-    query head h attends kv head h // (H // Hkv)."""
+    query head h attends kv head h // (H // Hkv).  ``window``: sliding
+    -window attention over the last ``window`` keys."""
 
     def __init__(self, hidden, num_heads, num_kv_heads=None,
-                 rope_theta=10000.0):
+                 rope_theta=10000.0, window=None):
         super().__init__()
         assert hidden % num_heads == 0
         self.num_heads = num_heads
@@ -58,16 +72,24 @@ class LlamaAttention(nn.Module):
         assert num_heads % self.num_kv_heads == 0
         self.head_dim = hidden // num_heads
         self.rope_theta = rope_theta
+        self.window = window
         self.qkv = nn.Linear(
             hidden, (num_heads + 2 * self.num_kv_heads) * self.head_dim,
             bias=False)
         self.proj = nn.Linear(hidden, hidden, bias=False)
 
-    def forward(self, x):
-        from easyparallellibrary_amd.ops.attention import flash_attention
+    def forward(self, x, segment_ids=None, bounds=None):
+        """bounds: the band_bounds of (segment_ids, self.window) where the
+        caller has computed them already (LlamaCore does, once for all
+        layers)"""
+        from easyparallellibrary_amd.ops.attention import (
+            band_bounds, flash_attention)
         from easyparallellibrary_amd.ops.rope import (
             apply_rope, rope_qkv_flash_attention, rope_qkv_native_ok)
         b, s, h = x.shape
+        if bounds is None and not (segment_ids is None
+                                   and self.window is None):
+            bounds = band_bounds(segment_ids, self.window, s, x.device)
         qkv = self.qkv(x)
         hq, hkv = self.num_heads, self.num_kv_heads
         if rope_qkv_native_ok(qkv, hq, hkv):
@@ -75,32 +97,33 @@ class LlamaAttention(nn.Module):
             # the attention kernels read its strided slices
             o = rope_qkv_flash_attention(qkv, causal=True,
                                          theta=self.rope_theta,
-                                         num_heads=hq, num_kv_heads=hkv)
+                                         num_heads=hq, num_kv_heads=hkv,
+                                         bounds=bounds)
         else:
             q, k, v = (t.transpose(1, 2) for t in qkv.reshape(
                 b, s, hq + 2 * hkv, self.head_dim).split(
                     [hq, hkv, hkv], dim=2))
             q = apply_rope(q, theta=self.rope_theta)
             k = apply_rope(k, theta=self.rope_theta)
-            o = flash_attention(q, k, v, causal=True)
+            o = flash_attention(q, k, v, causal=True, bounds=bounds)
         return self.proj(o.transpose(1, 2).reshape(b, s, h))
 
 
 class LlamaBlock(nn.Module):
     def __init__(self, hidden, num_heads, ffn_hidden, rope_theta=10000.0,
-                 eps=1e-5, num_kv_heads=None):
+                 eps=1e-5, num_kv_heads=None, window=None):
         super().__init__()
         self.rms1 = FusedRMSNorm(hidden, eps=eps)
         self.attn = LlamaAttention(hidden, num_heads, num_kv_heads,
-                                   rope_theta=rope_theta)
+                                   rope_theta=rope_theta, window=window)
         self.rms2 = FusedRMSNorm(hidden, eps=eps)
         # gate and up projections as ONE GEMM: columns [0, F) gate, [F, 2F) up
         self.fc12 = nn.Linear(hidden, 2 * ffn_hidden, bias=False)
         self.act = FusedSwiGLU()
         self.fc2 = nn.Linear(ffn_hidden, hidden, bias=False)
 
-    def forward(self, x):
-        a = self.attn(self.rms1(x))
+    def forward(self, x, segment_ids=None, bounds=None):
+        a = self.attn(self.rms1(x), segment_ids, bounds)
         # residual add fused into rms2; the summed stream s is the
         # residual carried forward
         y, s = self.rms2.forward_with_sum(a, x)
@@ -133,20 +156,39 @@ class LlamaHead(nn.Module):
 
 class LlamaCore(nn.Module):
     def __init__(self, layers, hidden, heads, ffn, vocab_size,
-                 rope_theta=10000.0, kv_heads=None):
+                 rope_theta=10000.0, kv_heads=None, window=None):
         super().__init__()
+        self.window = window
         self.embeddings = LlamaEmbedding(vocab_size, hidden)
         self.blocks = nn.ModuleList(
             LlamaBlock(hidden, heads, ffn, rope_theta=rope_theta,
-                       num_kv_heads=kv_heads)
+                       num_kv_heads=kv_heads, window=window)
             for _ in range(layers))
         self.head = LlamaHead(hidden, vocab_size)
 
-    def forward(self, ids):
+    def forward(self, ids, segment_ids=None):
+        from easyparallellibrary_amd.ops.attention import band_bounds
         x = self.embeddings(ids)
+        bounds = None
+        if segment_ids is not None or self.window is not None:
+            # once per forward, shared by every layer
+            bounds = band_bounds(segment_ids, self.window, ids.shape[1],
+                                 x.device)
         for b in self.blocks:
-            x = b(x)
+            x = b(x, segment_ids, bounds)
         return self.head(x)
+
+
+class _StagedLlama(StagedModel):
+    """The pipeline stages pass one tensor along: a config's ``window``
+    works (a module attribute), ``segment_ids`` does not."""
+
+    def forward(self, ids, segment_ids=None):
+        if segment_ids is not None:
+            raise NotImplementedError(
+                "segment_ids with num_stages > 1: the staged model threads "
+                "one tensor through its stages")
+        return super().forward(ids)
 
 
 def build_llama(config="llama-7b", vocab_size=32000, max_pos=2048,
@@ -158,10 +200,11 @@ def build_llama(config="llama-7b", vocab_size=32000, max_pos=2048,
     cfg = LLAMA_CONFIGS[config] if isinstance(config, str) else dict(config)
     L, H, A, F = cfg["layers"], cfg["hidden"], cfg["heads"], cfg["ffn"]
     KV = cfg.get("kv_heads")
+    W = cfg.get("window")
     if num_stages <= 1:
         with epl.replicate(device_count=1, name="stage_0"):
             model = LlamaCore(L, H, A, F, vocab_size, rope_theta=rope_theta,
-                              kv_heads=KV)
+                              kv_heads=KV, window=W)
         model.max_pos = max_pos
         return init_weights(model)
     per = (L + num_stages - 1) // num_stages
@@ -174,12 +217,12 @@ def build_llama(config="llama-7b", vocab_size=32000, max_pos=2048,
                 mods.append(LlamaEmbedding(vocab_size, H))
             n = min(per, L - layer_idx)
             mods.extend(LlamaBlock(H, A, F, rope_theta=rope_theta,
-                                   num_kv_heads=KV)
+                                   num_kv_heads=KV, window=W)
                         for _ in range(n))
             layer_idx += n
             if s == num_stages - 1:
                 mods.append(LlamaHead(H, vocab_size))
             stages.append(_Stage(mods))
-    model = StagedModel(stages)
+    model = _StagedLlama(stages)
     model.max_pos = max_pos
     return init_weights(model)

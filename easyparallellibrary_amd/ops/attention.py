@@ -24,6 +24,31 @@ K / V where they are and sum dk / dv over a group's heads in registers:
 nothing is expanded and the gradients come back in the kv shape.  They
 have no dropout: a GQA call with dropout_p > 0 (like fp32 and the CPU)
 expands k and v and takes the torch path, where autograd does the sum.
+
+Banded causal attention (packed documents, sliding windows):
+``flash_attention`` and ``rope_qkv_flash_attention`` take ``segment_ids``
+(int [B, S]) and ``window`` (int >= 1), causal only — with causal=False
+either raises ValueError.  For sample b with len = clamp(seqlens[b], 0, S)
+(len = S without seqlens), query i < len attends key j iff
+
+    kv_lo[b, i] <= j <= i,   kv_lo[b, i] = max(seg_start[b, i], i - window + 1, 0)
+
+A document is a maximal run of equal consecutive ids: ids need not be
+sorted or unique, and nothing is checked on the host.  seg_start[b, i] is
+the first index of the document that holds i, seg_end[b, i] one past its
+last.  The kv-parallel backward kernels use the inverse bound
+q_hi[b, j] = min(seg_end[b, j], j + window, S): key j is seen by queries
+j <= i < min(q_hi[b, j], len).  Either argument may be None (no
+restriction from it).  Rows >= len stay exact zeros; every valid row sees
+at least itself, so no row is empty.  RoPE positions keep counting along
+the row — they do NOT restart per document.  For finite inputs a
+document's outputs and gradients do not depend on any other document of
+the row.  The kernels (csrc/kernels/attention_band.hip) skip the tiles a
+band excludes and serve any Hkv dividing H; dropout, fp32 and the CPU
+take the torch path with the same semantics, its boolean mask built from
+the same kv_lo.  ``band_bounds`` computes (kv_lo, q_hi) with torch ops and
+no host sync; a caller with many layers computes them once and passes
+``bounds=(kv_lo, q_hi)`` instead.
 """
 
 import os
@@ -217,6 +242,92 @@ class _FlashAttentionGQA(torch.autograd.Function):
         return dq, dk, dv, None, None, None
 
 
+def band_bounds(segment_ids, window, seq, device):
+    """(kv_lo, q_hi) of the module docstring: int32, contiguous, [B, S], or
+    [1, S] when ``segment_ids`` is None (the kernels broadcast one row over
+    the batch).  torch ops only, no host sync: a captured step replays
+    with whatever ids the tensor then holds."""
+    pos = torch.arange(seq, device=device, dtype=torch.int32)[None, :]
+    kv_lo, q_hi = torch.zeros_like(pos), torch.full_like(pos, seq)
+    if segment_ids is not None:
+        if segment_ids.dim() != 2 or segment_ids.shape[1] != seq \
+                or segment_ids.dtype.is_floating_point:
+            raise ValueError("segment_ids must be an int tensor [B, S={}], "
+                             "got {} {}".format(seq, segment_ids.dtype,
+                                                tuple(segment_ids.shape)))
+        ids = segment_ids      # on ``device`` already: no hidden copy
+        change = ids[:, 1:] != ids[:, :-1]
+        edge = torch.ones_like(change[:, :1])
+        # a document starts at 0 and after every change: its start is the
+        # running maximum of the start positions, its end the mirror image
+        starts = torch.where(torch.cat([edge, change], 1), pos, 0)
+        ends = torch.where(torch.cat([change, edge], 1), pos + 1, seq)
+        kv_lo = starts.cummax(1).values
+        q_hi = ends.flip(1).cummin(1).values.flip(1)
+    if window is not None:
+        if int(window) < 1:
+            raise ValueError("window must be >= 1, got {}".format(window))
+        kv_lo = torch.maximum(kv_lo, (pos - (int(window) - 1)).clamp(min=0))
+        q_hi = torch.minimum(q_hi, (pos + int(window)).clamp(max=seq))
+    return kv_lo.int().contiguous(), q_hi.int().contiguous()
+
+
+def _check_bounds(bounds, q):
+    kv_lo, q_hi = bounds
+    for t in (kv_lo, q_hi):
+        if t.dtype != torch.int32 or t.dim() != 2 \
+                or t.shape[0] not in (1, q.shape[0]) \
+                or t.shape[1] != q.shape[-2] or t.shape != kv_lo.shape:
+            raise ValueError("bounds must be two int32 [B or 1, S] tensors")
+        if t.device != q.device:
+            raise ValueError("bounds must be on the device of q")
+    return kv_lo.contiguous(), q_hi.contiguous()
+
+
+class _FlashAttentionBand(torch.autograd.Function):
+    """Banded causal flash attention: q [B, H, S, D], k / v [B, Hkv, S, D]
+    with Hkv dividing H (MHA included), any kernel-ok strides consumed in
+    place; kv_lo / q_hi from band_bounds.  Gradients are written in the
+    input layout, dk and dv in the kv shape."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, kv_lo, q_hi, seqlens=None):
+        if not _kernel_ok(q):
+            q = q.contiguous()
+        if not (_kernel_ok(k) and _kernel_ok(v)
+                and k.stride() == v.stride()):
+            k, v = k.contiguous(), v.contiguous()
+        b, h, seq, d = q.shape
+        out = torch.empty(b, seq, h, d, dtype=q.dtype,
+                          device=q.device).permute(0, 2, 1, 3)
+        lse = torch.empty(b * h * seq, dtype=torch.float32,
+                          device=q.device)
+        native_ext().attn_fwd_band(q, k, v, out, lse, scale, kv_lo, seqlens)
+        ctx.has_seqlens = seqlens is not None
+        ctx.save_for_backward(q, k, v, out, lse, kv_lo, q_hi, *[
+            t for t in (seqlens,) if t is not None])
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
+        q, k, v, out, lse, kv_lo, q_hi = saved[:7]
+        seqlens = saved[7] if ctx.has_seqlens else None
+        if not _kernel_ok(dout):
+            dout = dout.contiguous()
+        dq = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype,
+                                 device=q.device)
+        dk = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype,
+                                 device=k.device)
+        dv = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype,
+                                 device=k.device)
+        delta = torch.empty_like(lse)
+        native_ext().attn_bwd_band(q, k, v, out, dout, lse, delta, dq, dk,
+                                   dv, ctx.scale, kv_lo, q_hi, seqlens)
+        return dq, dk, dv, None, None, None, None
+
+
 class _QKVFlashAttention(torch.autograd.Function):
     """Module-level fused path: consumes the [B,S,3,H,D] qkv projection
     buffer directly.  Forward feeds the kernels the q/k/v strided views
@@ -333,21 +444,28 @@ def flash_attention_with_lse(q, k, v, causal=False, scale=None):
     return out, lse
 
 
-def _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens):
-    """The padded-batch semantics of the kernels in torch ops (CPU and
-    non-native shapes): a key mask, then zeros on the padded query rows.
-    An empty sample is masked as if it held one key, so its softmax rows
-    are finite and the ``where`` below hands no NaN to the backward; its
-    rows are all padding and come out zero like any other.  The padded
-    rows of q, k, v are replaced by zeros first: a masked NaN would
-    otherwise come through the matmuls as 0 * NaN."""
+def _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens, kv_lo=None):
+    """The padded-batch (and banded, ``kv_lo`` [B or 1, S]) semantics of
+    the kernels in torch ops (CPU and non-native shapes): a key mask, then
+    zeros on the padded query rows.  A padded row keeps its own diagonal
+    key (an empty sample: key 0), so its softmax row is finite and the
+    ``where`` below hands no NaN to the backward; such rows come out zero
+    like any other.  The padded rows of q, k, v are replaced by zeros
+    first: a masked NaN would otherwise come through the matmuls as
+    0 * NaN."""
     seq = q.shape[-2]
-    lens = seqlens.clamp(0, seq)
     pos = torch.arange(seq, device=q.device)
+    if seqlens is None:
+        lens = torch.full((q.shape[0],), seq, device=q.device)
+    else:
+        lens = seqlens.clamp(0, seq)
     keys = pos[None, :] < lens.clamp(min=1)[:, None]          # [B, S]
     attn_mask = keys[:, None, None, :]
     if causal:
         attn_mask = attn_mask & (pos[None, :] <= pos[:, None])
+    if kv_lo is not None:
+        attn_mask = (attn_mask & (pos >= kv_lo[:, None, :, None])) \
+            | (pos[None, :] == pos[:, None])
     rows = (pos[None, :] < lens[:, None])[:, None, :, None]    # [B,1,S,1]
     q, k, v = (torch.where(rows, t, torch.zeros_like(t)) for t in (q, k, v))
     out = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask,
@@ -377,13 +495,18 @@ def qkv_native_ok(qkv):
 
 
 def flash_attention(q, k, v, causal=False, scale=None, allow_native=True,
-                    dropout_p=0.0, seqlens=None):
+                    dropout_p=0.0, seqlens=None, segment_ids=None,
+                    window=None, bounds=None):
     """q: [B, H, S, D]; k, v: [B, Hkv, S, D] with Hkv dividing H (grouped
     -query attention when Hkv < H, module docstring).  Native kernel when
     bf16/D=64|128 on GPU; torch SDPA otherwise.  dropout_p runs in-kernel
     on the native path (training-mode callers only; not with GQA).
     seqlens: int32 [B] valid lengths of a right-padded batch (module
-    docstring); the fallback keeps the same semantics."""
+    docstring); the fallback keeps the same semantics.
+    segment_ids (int [B, S]) / window (int): banded causal attention over
+    packed documents / a sliding window (module docstring), causal only,
+    native for any Hkv without dropout.  bounds: the (kv_lo, q_hi) that
+    ``band_bounds`` returns for them, computed once by the caller."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     seqlens = _check_seqlens(seqlens, q)
@@ -393,15 +516,29 @@ def flash_attention(q, k, v, causal=False, scale=None, allow_native=True,
         raise ValueError(
             "k and v must share a head count that divides q's {}, got {} "
             "and {}".format(heads, kv_heads, v.shape[1]))
+    banded = not (segment_ids is None and window is None and bounds is None)
+    if banded:
+        if not causal:
+            raise ValueError("segment_ids / window need causal=True: a "
+                             "non-causal band is not supported")
+        if bounds is None:
+            bounds = band_bounds(segment_ids, window, q.shape[-2], q.device)
+        bounds = _check_bounds(bounds, q)
     if allow_native and use_native(q):
         if q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
-            if kv_heads == heads:
+            if banded:
+                if not dropout_p:
+                    return _FlashAttentionBand.apply(q, k, v, scale,
+                                                     *bounds, seqlens)
+                _warn_fallback("banded attention with dropout")
+            elif kv_heads == heads:
                 return _FlashAttention.apply(q, k, v, causal, scale,
                                              dropout_p, seqlens)
-            if not dropout_p:
+            elif not dropout_p:
                 return _FlashAttentionGQA.apply(q, k, v, causal, scale,
                                                 seqlens)
-            _warn_fallback("grouped-query attention with dropout")
+            else:
+                _warn_fallback("grouped-query attention with dropout")
         else:
             _warn_fallback("dtype={} head_dim={}".format(q.dtype,
                                                          q.shape[-1]))
@@ -409,6 +546,9 @@ def flash_attention(q, k, v, causal=False, scale=None, allow_native=True,
         # autograd sums the expanded gradients over each group
         k = k.repeat_interleave(heads // kv_heads, dim=1)
         v = v.repeat_interleave(heads // kv_heads, dim=1)
+    if banded:
+        return _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens,
+                            bounds[0])
     if seqlens is not None:
         return _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens)
     return F.scaled_dot_product_attention(q, k, v, is_causal=causal,

@@ -23,7 +23,8 @@ table exists by then and a captured forward only reads it.
 import torch
 
 from easyparallellibrary_amd.ops.attention import (
-    _check_seqlens, _drop_params, _kernel_ok, _mask_tensor, _saved_optionals)
+    _check_bounds, _check_seqlens, _drop_params, _kernel_ok, _mask_tensor,
+    _saved_optionals, band_bounds)
 from easyparallellibrary_amd.ops.dispatch import native_ext, use_native
 
 _TABLES = {}
@@ -115,7 +116,10 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
     attention forward on the strided slices; the saved buffer is the
     rotated one, which is what the backward needs.  Backward lets the
     attention backward write into the slices of its own fresh d_qkv,
-    rotates the dq / dk heads back in place and returns it."""
+    rotates the dq / dk heads back in place and returns it.
+
+    ``kv_lo`` / ``q_hi`` (band_bounds) select the banded causal kernels,
+    for any Hkv; both None is the plain path."""
 
     @staticmethod
     def _slices(buf, heads, kv_heads):
@@ -127,7 +131,7 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, heads, kv_heads, causal, scale, dropout_p,
-                seqlens, cos, sin, pos0):
+                seqlens, cos, sin, pos0, kv_lo=None, q_hi=None):
         b, s, width = qkv.shape
         d = width // (heads + 2 * kv_heads)
         ctx.mark_dirty(qkv)
@@ -141,7 +145,10 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
                           device=qkv.device)
         thresh, inv_keep, seed = _drop_params(dropout_p)
         mask = _mask_tensor(b, heads, s, qkv.device) if thresh else None
-        if kv_heads == heads:
+        if kv_lo is not None:
+            native_ext().attn_fwd_band(q, k, v, out, lse, scale, kv_lo,
+                                       seqlens)
+        elif kv_heads == heads:
             native_ext().attn_fwd(q, k, v, out, lse, scale, causal, mask,
                                   seed, thresh, inv_keep, seqlens)
         else:
@@ -149,8 +156,9 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
                                       seqlens)
         ctx.has_mask = mask is not None
         ctx.has_seqlens = seqlens is not None
+        ctx.banded = kv_lo is not None
         ctx.save_for_backward(qkv, out, lse, cos, sin, *[
-            t for t in (mask, seqlens) if t is not None])
+            t for t in (mask, seqlens, kv_lo, q_hi) if t is not None])
         ctx.heads, ctx.kv_heads = heads, kv_heads
         ctx.causal, ctx.scale = causal, scale
         ctx.inv_keep, ctx.pos0 = inv_keep, pos0
@@ -162,6 +170,7 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
         saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
         qkv, out, lse, cos, sin = saved[:5]
         mask, seqlens = _saved_optionals(ctx, saved[5:])
+        kv_lo, q_hi = saved[-2:] if ctx.banded else (None, None)
         b, s, width = qkv.shape
         heads, kv_heads = ctx.heads, ctx.kv_heads
         d = width // (heads + 2 * kv_heads)
@@ -177,7 +186,11 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
             dq, dk, dv = _RopeQKVFlashAttention._slices(dpacked, heads,
                                                         kv_heads)
             delta = torch.empty_like(lse)
-            if kv_heads == heads:
+            if ctx.banded:
+                native_ext().attn_bwd_band(q, k, v, out, dout, lse, delta,
+                                           dq, dk, dv, ctx.scale, kv_lo,
+                                           q_hi, seqlens)
+            elif kv_heads == heads:
                 native_ext().attn_bwd(q, k, v, out, dout, lse, delta, dq, dk,
                                       dv, ctx.scale, ctx.causal, True, mask,
                                       ctx.inv_keep, None, seqlens)
@@ -191,7 +204,7 @@ class _RopeQKVFlashAttention(torch.autograd.Function):
             dqkv += drot
         native_ext().rope_(dpacked[:, :, :heads + kv_heads], cos, sin,
                            ctx.pos0, True)
-        return dqkv, None, None, None, None, None, None, None, None, None
+        return (dqkv,) + (None,) * 11
 
 
 def rope_qkv_native_ok(qkv, heads, kv_heads=None):
@@ -215,7 +228,8 @@ def rope_qkv_native_ok(qkv, heads, kv_heads=None):
 
 def rope_qkv_flash_attention(qkv, causal=True, dropout_p=0.0, seqlens=None,
                              pos0=0, theta=10000.0, scale=None,
-                             num_heads=None, num_kv_heads=None):
+                             num_heads=None, num_kv_heads=None,
+                             segment_ids=None, window=None, bounds=None):
     """Rotary embedding of q and k, then flash attention, on the packed
     projection output.  Native kernels only (rope_qkv_native_ok); callers
     use apply_rope + flash_attention otherwise.
@@ -235,7 +249,12 @@ def rope_qkv_flash_attention(qkv, causal=True, dropout_p=0.0, seqlens=None,
 
     Returns the attention output as a [B, H, S, D] view whose memory order
     is [B, S, H, D].  dropout_p, seqlens: as qkv_flash_attention.  pos0:
-    position of the first token."""
+    position of the first token.
+
+    segment_ids / window / bounds: banded causal attention as in
+    ``flash_attention`` (ops/attention.py), causal only and without
+    dropout here.  Positions keep counting along the row: they do not
+    restart per document."""
     if qkv.dim() == 5:
         b, s, _, heads, d = qkv.shape
         if num_heads is not None and num_heads != heads:
@@ -261,11 +280,24 @@ def rope_qkv_flash_attention(qkv, causal=True, dropout_p=0.0, seqlens=None,
             "bf16 qkv on the GPU with head_dim 64 or 128")
     if kv_heads != heads and dropout_p:
         raise ValueError("the grouped-query kernels have no dropout")
+    banded = not (segment_ids is None and window is None and bounds is None)
+    if banded and not causal:
+        raise ValueError("segment_ids / window need causal=True: a "
+                         "non-causal band is not supported")
+    if banded and dropout_p:
+        raise ValueError("the banded kernels have no dropout")
     if scale is None:
         scale = d ** -0.5
     seqlens = _check_seqlens(seqlens, flat)
     cos, sin = rope_tables(flat.device, d, theta, pos0 + s)
+    if banded:
+        if bounds is None:
+            bounds = band_bounds(segment_ids, window, s, flat.device)
+        bounds = _check_bounds(bounds, flat.view(b, s, heads + 2 * kv_heads,
+                                                 d).transpose(1, 2))
+    else:
+        bounds = (None, None)
     out, _ = _RopeQKVFlashAttention.apply(flat, heads, kv_heads, causal,
                                           scale, dropout_p, seqlens, cos,
-                                          sin, pos0)
+                                          sin, pos0, *bounds)
     return out

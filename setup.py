@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "csrc/kernels/mfma_probe.hip",
         "csrc/kernels/attention.hip",
         "csrc/kernels/attention_gqa.hip",
+        "csrc/kernels/attention_band.hip",
     ],
     include_dirs=[os.path.join(ROCM, "include")],
     library_dirs=[os.path.join(ROCM, "lib")],
