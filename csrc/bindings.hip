@@ -69,6 +69,8 @@ void epl_moe_combine_bwd(void*, float*, const void*, const void*,
                          const float*, const int64_t*, const int64_t*,
                          const int64_t*, int64_t, int64_t, int64_t,
                          hipStream_t);
+void epl_moe_gemm(int, void*, const void*, const void*, const int*, void*,
+                  int64_t, int64_t, int64_t, int64_t, hipStream_t);
 int64_t epl_moe_router_waves(int64_t, int64_t);
 void epl_moe_router_fwd(const void*, int64_t*, float*, float*, int64_t*,
                         float*, float*, float*, int*, int64_t, int64_t,
@@ -1035,6 +1037,91 @@ void moe_router_bwd(at::Tensor dlogits, at::Tensor logits, at::Tensor lse,
                      cur_stream());
 }
 
+// Grouped expert GEMMs (csrc/kernels/moe_gemm.hip).  Metadata checks only:
+// no value is read on the host, so a captured step replays with whatever
+// rows then holds.
+static void check_moe_gemm(const at::Tensor& t, const at::Device& dev,
+                           int64_t d0, int64_t d1, int64_t d2,
+                           const char* name) {
+  check(t, at::kBFloat16, name);
+  TORCH_CHECK(t.device() == dev, name, " is on another device");
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == d0 && t.size(1) == d1 &&
+              t.size(2) == d2, name, " must be [", d0, ", ", d1, ", ", d2,
+              "], got ", t.sizes());
+  check_aligned(t, 16, name);
+}
+
+// form 0 nn: a [E,M,K] b [E,K,N] c [E,M,N]; 1 nt: a [E,M,N] b [E,K,N]
+// c [E,M,K]; 2 tn: a [E,M,K] b [E,M,N] c [E,K,N].  aux is shaped like c.
+static void moe_gemm(int form, at::Tensor& c, const at::Tensor& a,
+                     const at::Tensor& b,
+                     const c10::optional<at::Tensor>& rows,
+                     const c10::optional<at::Tensor>& aux,
+                     const char* aux_name) {
+  TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && c.dim() == 3,
+              "moe_gemm operands must be 3-D");
+  const at::Device dev = a.device();
+  const int64_t E = a.size(0), M = a.size(1);
+  const int64_t K = form == 1 ? b.size(1) : a.size(2);
+  const int64_t N = b.size(2);
+  TORCH_CHECK(E >= 1 && M >= 1, "moe_gemm needs E >= 1 and M >= 1");
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && N >= 64 && N % 64 == 0,
+              "moe_gemm needs K and N to be multiples of 64, got K = ", K,
+              ", N = ", N);
+  if (form == 0) {
+    check_moe_gemm(a, dev, E, M, K, "a");
+    check_moe_gemm(b, dev, E, K, N, "b");
+    check_moe_gemm(c, dev, E, M, N, "c");
+  } else if (form == 1) {
+    check_moe_gemm(a, dev, E, M, N, "a");
+    check_moe_gemm(b, dev, E, K, N, "b");
+    check_moe_gemm(c, dev, E, M, K, "c");
+  } else {
+    check_moe_gemm(a, dev, E, M, K, "a");
+    check_moe_gemm(b, dev, E, M, N, "b");
+    check_moe_gemm(c, dev, E, K, N, "c");
+  }
+  if (aux.has_value())
+    check_moe_gemm(*aux, dev, c.size(0), c.size(1), c.size(2), aux_name);
+  // the grid is dim3(row tiles, E * column tiles) of 128 x 128 tiles and
+  // the kernels index rows and columns in 32 bits
+  const int64_t P = c.size(1), Q = c.size(2);
+  TORCH_CHECK(M < (int64_t(1) << 30) && K < (int64_t(1) << 30) &&
+              N < (int64_t(1) << 30) && (P + 127) / 128 <= 65535 &&
+              E * ((Q + 127) / 128) <= 65535,
+              "moe_gemm shape exceeds the launch grid");
+  const int* rows_ptr = nullptr;
+  if (rows.has_value()) {
+    const at::Tensor& r = *rows;
+    TORCH_CHECK(r.is_cuda() && r.device() == dev,
+                "rows must be a tensor on the operands' device");
+    TORCH_CHECK(r.scalar_type() == at::kInt && r.is_contiguous() &&
+                r.dim() == 1 && r.size(0) == E,
+                "rows must be a contiguous int32 tensor of [", E, "]");
+    rows_ptr = r.data_ptr<int>();
+  }
+  epl_moe_gemm(form, c.data_ptr(), a.data_ptr(), b.data_ptr(), rows_ptr,
+               aux.has_value() ? aux->data_ptr() : nullptr, E, M, K, N,
+               cur_stream());
+}
+
+void moe_gemm_nn(at::Tensor c, at::Tensor a, at::Tensor b,
+                 c10::optional<at::Tensor> rows,
+                 c10::optional<at::Tensor> act) {
+  moe_gemm(0, c, a, b, rows, act, "act");
+}
+
+void moe_gemm_nt(at::Tensor c, at::Tensor a, at::Tensor b,
+                 c10::optional<at::Tensor> rows,
+                 c10::optional<at::Tensor> pre) {
+  moe_gemm(1, c, a, b, rows, pre, "pre");
+}
+
+void moe_gemm_tn(at::Tensor c, at::Tensor a, at::Tensor b,
+                 c10::optional<at::Tensor> rows) {
+  moe_gemm(2, c, a, b, rows, c10::nullopt, "");
+}
+
 void colsum(at::Tensor dy, at::Tensor db, at::Tensor partial) {
   const bool bf16 = is_bf16(dy);
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 2,
@@ -1343,6 +1430,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_dispatch_bwd", &moe_dispatch_bwd);
   m.def("moe_combine_fwd", &moe_combine_fwd);
   m.def("moe_combine_bwd", &moe_combine_bwd);
+  m.def("moe_gemm_nn", &moe_gemm_nn, py::arg("c"), py::arg("a"),
+        py::arg("b"), py::arg("rows") = py::none(),
+        py::arg("act") = py::none());
+  m.def("moe_gemm_nt", &moe_gemm_nt, py::arg("c"), py::arg("a"),
+        py::arg("b"), py::arg("rows") = py::none(),
+        py::arg("pre") = py::none());
+  m.def("moe_gemm_tn", &moe_gemm_tn, py::arg("c"), py::arg("a"),
+        py::arg("b"), py::arg("rows") = py::none());
   m.def("moe_router_fwd", &moe_router_fwd);
   m.def("moe_router_bwd", &moe_router_bwd);
   m.def("moe_router_waves", [](int64_t n, int64_t e) {

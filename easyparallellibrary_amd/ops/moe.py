@@ -43,7 +43,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from easyparallellibrary_amd.comm import functional
-from easyparallellibrary_amd.ops.dispatch import native_ext, use_native
+from easyparallellibrary_amd.ops.dispatch import (native_available,
+                                                  native_ext, use_native)
 
 
 def _moe_bmm():
@@ -54,6 +55,11 @@ def _moe_bmm():
 def _moe_native_dispatch():
     import os
     return os.environ.get("EPL_MOE_NATIVE_DISPATCH", "1") == "1"
+
+
+def _moe_native_gemm_env():
+    import os
+    return os.environ.get("EPL_MOE_NATIVE_GEMM", "0") == "1"
 
 
 def _moe_fused_router_env():
@@ -267,6 +273,55 @@ class _BatchedExpertLinear(torch.autograd.Function):
         return gx, gw
 
 
+class _GroupedExpertLinear(torch.autograd.Function):
+    """The expert FFN h = gelu(x w1) w2 on the grouped GEMM kernels
+    (csrc/kernels/moe_gemm.hip): both linears and their four backward
+    GEMMs, GeLU and its derivative fused into the epilogues, no torch.bmm
+    and no copy of w2^T.
+
+    x [E, M, hidden], w1 [E, hidden, ffn], w2 [E, ffn, hidden], all bf16;
+    rows: None or int32 [E] on the device, expert e holding rows[e]
+    (clamped to [0, M] in the kernels) live leading rows.  Dead rows of x
+    and of the incoming gradient are never read, dead rows of h and of
+    dx are +0, and the weight gradients sum over the live rows only.
+
+    forward:  pre, act = nn(x, w1) with act = gelu(pre);  h = nn(act, w2)
+    backward: dpre = nt(dh, w2) * gelu'(pre);  dw2 = tn(act, dh)
+              dx = nt(dpre, w1);               dw1 = tn(x, dpre)"""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, rows):
+        ext = native_ext()
+        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
+        e, m, _ = x.shape
+        pre = x.new_empty(e, m, w1.shape[2])
+        act = torch.empty_like(pre)
+        ext.moe_gemm_nn(pre, x, w1, rows, act)
+        h = x.new_empty(e, m, w2.shape[2])
+        ext.moe_gemm_nn(h, act, w2, rows)
+        ctx.save_for_backward(x, w1, w2, pre, act)
+        ctx.rows = rows
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        ext = native_ext()
+        x, w1, w2, pre, act = ctx.saved_tensors
+        rows = ctx.rows
+        dh = dh.contiguous()
+        dpre = torch.empty_like(pre)
+        ext.moe_gemm_nt(dpre, dh, w2, rows, pre)
+        dw2 = torch.empty_like(w2)
+        ext.moe_gemm_tn(dw2, act, dh, rows)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            ext.moe_gemm_nt(dx, dpre, w1, rows)
+        dw1 = torch.empty_like(w1)
+        ext.moe_gemm_tn(dw1, x, dpre, rows)
+        return dx, dw1, dw2, None
+
+
 class ExpertParallelMLP(nn.Module):
     """num_experts split across the comm group; each rank holds
     num_experts // world experts (reference tests use the same layout,
@@ -274,7 +329,7 @@ class ExpertParallelMLP(nn.Module):
 
     def __init__(self, hidden, ffn_hidden, num_experts, comm=None, top_k=2,
                  capacity_factor=1.25, aux_loss_coef=0.0, z_loss_coef=0.0,
-                 fused_router=None):
+                 fused_router=None, expert_gemm=None):
         """aux_loss_coef / z_loss_coef: weights of the load-balance loss
         L_bal and the router z loss L_z (module docstring) in the
         gradient; the step's reported loss stays the task loss.
@@ -282,8 +337,16 @@ class ExpertParallelMLP(nn.Module):
         coefficient is non-zero and they apply (native build, device
         tensor, bf16/fp32 logits, top_k <= 2, 2 <= num_experts <= 256);
         True / False force the choice, as EPL_MOE_FUSED_ROUTER=1/0 does
-        for modules built with None."""
+        for modules built with None.
+        expert_gemm: True = the expert FFN on the native grouped GEMM
+        kernels (_GroupedExpertLinear: live rows only at world 1, fused
+        GeLU); it needs the native build, bf16 device tensors and hidden
+        and ffn_hidden multiples of 64, and raises where it does not
+        apply.  False = the torch.bmm path.  None follows
+        EPL_MOE_NATIVE_GEMM (read at call time, default 0), using the
+        kernels where they apply."""
         super().__init__()
+        self.expert_gemm = expert_gemm
         self.aux_loss_coef = float(aux_loss_coef)
         self.z_loss_coef = float(z_loss_coef)
         self.fused_router = fused_router
@@ -361,6 +424,24 @@ class ExpertParallelMLP(nn.Module):
                     "device tensor, top_k <= 2 and {} <= num_experts <= {}"
                     .format(ROUTER_MIN_EXPERTS, ROUTER_MAX_EXPERTS))
         return "torch" if has_aux else None
+
+    def _native_gemm(self, x):
+        """whether this call's expert FFN runs on the grouped GEMM kernels"""
+        want = self.expert_gemm
+        if want is None:
+            want = _moe_native_gemm_env()
+        if not want:
+            return False
+        can = (x.dtype == torch.bfloat16 and self.w1.dtype == torch.bfloat16
+               and self.hidden % 64 == 0 and self.ffn_hidden % 64 == 0
+               and x.is_cuda and native_available() and use_native(x))
+        if not can and self.expert_gemm:
+            raise RuntimeError(
+                "expert_gemm=True needs the native extension, bf16 device "
+                "tensors and weights, and hidden and ffn_hidden multiples "
+                "of 64 (hidden {}, ffn_hidden {}, dtype {})".format(
+                    self.hidden, self.ffn_hidden, x.dtype))
+        return can
 
     def _route(self, x, mode):
         logits = self.gate(x)
@@ -445,7 +526,16 @@ class ExpertParallelMLP(nn.Module):
         # expert FFN: batched GEMM (one hipBLASLt grouped call per
         # matmul, hand-written backward above) by default; EPL_MOE_BMM=0
         # falls back to the per-expert 2D-GEMM loop
-        if _moe_bmm():
+        if self._native_gemm(x):
+            # live rows per local expert: at world 1 the dispatch fills
+            # the first min(count, capacity) rows of each expert; with a
+            # group the counts of the other ranks are not known here and
+            # every row counts as live
+            rows = None
+            if self.world == 1:
+                rows = counts.clamp(max=capacity).to(torch.int32)
+            h = _GroupedExpertLinear.apply(d, self.w1, self.w2, rows)
+        elif _moe_bmm():
             he = F.gelu(_BatchedExpertLinear.apply(d.contiguous(), self.w1))
             h = _BatchedExpertLinear.apply(he, self.w2)
         else:

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "csrc/kernels/llama_ops.hip",
         "csrc/kernels/moe.hip",
         "csrc/kernels/moe_router.hip",
+        "csrc/kernels/moe_gemm.hip",
         "csrc/kernels/mfma_probe.hip",
         "csrc/kernels/attention.hip",
         "csrc/kernels/attention_gqa.hip",
