@@ -103,6 +103,19 @@ void epl_attn_bwd_band(const void*, const void*, const void*, const void*,
                        const int64_t*, const int64_t*, const int64_t*,
                        const int64_t*, const int*, const int*, const int*,
                        int64_t, hipStream_t);
+void epl_attn_fwd_interval(const void*, const void*, const void*, void*,
+                           float*, int64_t, int64_t, float, int64_t,
+                           int64_t, int64_t, const int64_t*, const int64_t*,
+                           const int64_t*, const int*, const int*,
+                           const int*, int64_t, hipStream_t);
+void epl_attn_bwd_interval(const void*, const void*, const void*,
+                           const void*, const void*, const float*, float*,
+                           void*, void*, void*, int64_t, int64_t, float,
+                           int64_t, int64_t, int64_t, const int64_t*,
+                           const int64_t*, const int64_t*, const int64_t*,
+                           const int64_t*, const int64_t*, const int*,
+                           const int*, const int*, const int*, const int*,
+                           int64_t, hipStream_t);
 void epl_rms_norm_fwd(void*, const void*, const void*, void*, const void*,
                       float*, int64_t, int64_t, float, hipStream_t);
 int64_t epl_rms_norm_bwd_parts(int64_t, int64_t);
@@ -816,6 +829,107 @@ void attn_bwd_band(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out,
                     q_hi.data_ptr<int>(), rows == 1 ? 0 : seq, cur_stream());
 }
 
+// Interval attention (attention_interval.hip): the band's shapes on the
+// non-causal grids (B * Hkv on y, n * G blocks on x), plus four per-row
+// bounds kv_lo / kv_hi / q_lo / q_hi, int32 [B or 1, S] contiguous on q's
+// device, all of one shape.  Only metadata is checked: the kernels clamp
+// every value they read, so there is no host sync.
+static int64_t attn_interval_shapes(const at::Tensor& q, const at::Tensor& k,
+                                    const at::Tensor& v, int64_t* kv_s,
+                                    const char* kname, const char* vname) {
+  const int64_t kv_heads = attn_band_shapes(q, k, v, kv_s, kname, vname);
+  const int64_t heads = q.size(1), seq = q.size(2);
+  attn_check_grid(q.size(0) * kv_heads, seq, false);
+  TORCH_CHECK((seq + 127) / 128 * (heads / kv_heads) <= 65535,
+              "attention: seq ", seq, " x group ", heads / kv_heads,
+              " exceeds the 65535 blocks of a batch-kv-head");
+  return kv_heads;
+}
+
+static int64_t attn_interval_bounds(
+    std::initializer_list<std::pair<const at::Tensor*, const char*>> bounds,
+    const at::Tensor& q) {
+  int64_t rows = -1;
+  for (const auto& [t, name] : bounds) {
+    check(*t, at::kInt, name);
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == q.size(2) &&
+                    (t->size(0) == q.size(0) || t->size(0) == 1),
+                name, " must be int32 [B or 1, S]");
+    TORCH_CHECK(t->device() == q.device(), name,
+                " must be on the device of q");
+    TORCH_CHECK(rows < 0 || t->size(0) == rows,
+                "the interval bounds must have the same shape");
+    rows = t->size(0);
+  }
+  return rows;
+}
+
+void attn_fwd_interval(at::Tensor q, at::Tensor k, at::Tensor v,
+                       at::Tensor out, at::Tensor lse, double scale,
+                       at::Tensor kv_lo, at::Tensor kv_hi,
+                       c10::optional<at::Tensor> seqlens) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
+              out.is_cuda() && out.scalar_type() == at::kBFloat16);
+  int64_t in_s[3], kv_s[3], o_s[3];
+  attn_strides(q, in_s, "q");
+  attn_strides(out, o_s, "out");
+  const int64_t kv_heads = attn_interval_shapes(q, k, v, kv_s, "k", "v");
+  TORCH_CHECK(out.sizes() == q.sizes(), "out must have q's shape");
+  check(lse, at::kFloat, "lse");
+  const int64_t heads = q.size(1), seq = q.size(2);
+  TORCH_CHECK(lse.numel() == q.size(0) * heads * seq, "lse size mismatch");
+  const int64_t rows = attn_interval_bounds(
+      {{&kv_lo, "kv_lo"}, {&kv_hi, "kv_hi"}}, q);
+  if (q.numel() == 0) return;
+  epl_attn_fwd_interval(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                        out.data_ptr(), lse.data_ptr<float>(),
+                        q.size(0) * heads, seq, (float)scale, heads,
+                        kv_heads, q.size(3), in_s, kv_s, o_s,
+                        attn_seqlens(seqlens, q), kv_lo.data_ptr<int>(),
+                        kv_hi.data_ptr<int>(), rows == 1 ? 0 : seq,
+                        cur_stream());
+}
+
+void attn_bwd_interval(at::Tensor q, at::Tensor k, at::Tensor v,
+                       at::Tensor out, at::Tensor dout, at::Tensor lse,
+                       at::Tensor delta_ws, at::Tensor dq, at::Tensor dk,
+                       at::Tensor dv, double scale, at::Tensor kv_lo,
+                       at::Tensor kv_hi, at::Tensor q_lo, at::Tensor q_hi,
+                       c10::optional<at::Tensor> seqlens) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
+  for (const at::Tensor* t : {&out, &dout, &dq})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 &&
+                    t->sizes() == q.sizes(),
+                "out/dout/dq must be bf16 GPU tensors of q's shape");
+  int64_t in_s[3], kv_s[3], o_s[3], do_s[3], g_s[3], gkv_s[3];
+  attn_strides(q, in_s, "q");
+  attn_strides(out, o_s, "out");
+  attn_strides(dout, do_s, "dout");
+  attn_strides(dq, g_s, "dq");
+  const int64_t kv_heads = attn_interval_shapes(q, k, v, kv_s, "k", "v");
+  attn_interval_shapes(q, dk, dv, gkv_s, "dk", "dv");
+  TORCH_CHECK(dk.sizes() == k.sizes(), "dk/dv must have k's shape");
+  check(lse, at::kFloat, "lse");
+  check(delta_ws, at::kFloat, "delta_ws");
+  const int64_t heads = q.size(1), seq = q.size(2);
+  TORCH_CHECK(lse.numel() == q.size(0) * heads * seq &&
+              delta_ws.numel() == lse.numel(), "lse/delta_ws size mismatch");
+  const int64_t rows = attn_interval_bounds(
+      {{&kv_lo, "kv_lo"}, {&kv_hi, "kv_hi"}, {&q_lo, "q_lo"},
+       {&q_hi, "q_hi"}}, q);
+  if (q.numel() == 0) return;
+  epl_attn_bwd_interval(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                        out.data_ptr(), dout.data_ptr(),
+                        lse.data_ptr<float>(), delta_ws.data_ptr<float>(),
+                        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                        q.size(0) * heads, seq, (float)scale, heads,
+                        kv_heads, q.size(3), in_s, kv_s, o_s, do_s, g_s,
+                        gkv_s, attn_seqlens(seqlens, q),
+                        kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(),
+                        q_lo.data_ptr<int>(), q_hi.data_ptr<int>(),
+                        rows == 1 ? 0 : seq, cur_stream());
+}
+
 // the group-aware block orders of the q-parallel GQA grids evaluated on
 // the host: non-causal int32 [n * G * BHkv, 2] (bh, blk) at each linear
 // id x + n * G * y; causal int32 [G * BHkv] bh at each x
@@ -1470,6 +1584,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delta_ws"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("scale"), py::arg("kv_lo"), py::arg("q_hi"),
         py::arg("seqlens") = py::none());
+  m.def("attn_fwd_interval", &attn_fwd_interval, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("scale"),
+        py::arg("kv_lo"), py::arg("kv_hi"),
+        py::arg("seqlens") = py::none());
+  m.def("attn_bwd_interval", &attn_bwd_interval, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("out"), py::arg("dout"), py::arg("lse"),
+        py::arg("delta_ws"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("scale"), py::arg("kv_lo"), py::arg("kv_hi"),
+        py::arg("q_lo"), py::arg("q_hi"), py::arg("seqlens") = py::none());
   m.def("rms_norm_fwd", &rms_norm_fwd, py::arg("out"), py::arg("x"),
         py::arg("res"), py::arg("s"), py::arg("gamma"), py::arg("rstd"),
         py::arg("eps"));

@@ -34,6 +34,14 @@ class BertCore(nn.Module):
     instead.  Logits at padded positions are meaningless; give them the
     target -100.
 
+    segment_ids: ``forward(ids, segment_ids=...)`` (int [B, S]) packs
+    several documents into a row instead of padding each to the row: a
+    document is a maximal run of equal consecutive ids, attention stays
+    inside it (interval attention, ops/attention.py) and its position
+    embeddings restart at its first token, so a document computes what it
+    computes alone in a row.  Combines with seqlens (the tail of the row
+    is padding).
+
     live_rows_bwd: see LMHead; build_bert turns it on (an MLM loss
     ignores most positions)."""
 
@@ -48,9 +56,18 @@ class BertCore(nn.Module):
             for _ in range(layers))
         self.head = LMHead(hidden, vocab_size, live_rows_bwd=live_rows_bwd)
 
-    def forward(self, ids, seqlens=None):
+    def forward(self, ids, seqlens=None, segment_ids=None):
         if seqlens is None and self.pad_token_id is not None:
             seqlens = (ids != self.pad_token_id).sum(1).int()
+        bounds, emb = None, {}
+        if segment_ids is not None:
+            from easyparallellibrary_amd.ops.attention import interval_bounds
+            # once per forward, shared by every layer; kv_lo is the start
+            # of each token's document
+            bounds = interval_bounds(segment_ids, None, ids.shape[1],
+                                     ids.device)
+            pos = torch.arange(ids.shape[1], device=ids.device)
+            emb = {"positions": pos[None, :] - bounds[0].long()}
         # Every LayerNorm output on the way has two consumers, the next
         # attention and the next residual.  Between plain post-LN Blocks
         # it travels as the pair of FusedLayerNorm.forward_pair (x for the
@@ -60,17 +77,20 @@ class BertCore(nn.Module):
         n = len(self.blocks)
         plain = [type(b) is Block and not b.pre_ln for b in self.blocks]
         if n and plain[0] and type(self.embeddings) is Embeddings:
-            x, x_res = self.embeddings(ids, pair_out=True)
+            x, x_res = self.embeddings(ids, pair_out=True, **emb)
         else:
-            x = x_res = self.embeddings(ids)
+            x = x_res = self.embeddings(ids, **emb)
         for i, b in enumerate(self.blocks):
             if plain[i]:
                 # the last block's output has one consumer, the head
                 pair_out = i + 1 < n and plain[i + 1]
-                x = b(x, seqlens=seqlens, x_res=x_res, pair_out=pair_out)
+                x = b(x, seqlens=seqlens, x_res=x_res, pair_out=pair_out,
+                      bounds=bounds)
                 x, x_res = x if pair_out else (x, x)
             else:
-                x = b(x) if seqlens is None else b(x, seqlens=seqlens)
+                kw = {k: v for k, v in (("seqlens", seqlens),
+                                        ("bounds", bounds)) if v is not None}
+                x = b(x, **kw)
                 x_res = x
         return self.head(x)
 
@@ -86,6 +106,18 @@ class StagedModel(nn.Module):
         for s in self.stages:
             x = s(x)
         return x
+
+
+class _StagedBert(StagedModel):
+    """The pipeline stages pass one tensor along, so ``segment_ids``
+    cannot reach the attention of the later stages."""
+
+    def forward(self, ids, segment_ids=None):
+        if segment_ids is not None:
+            raise NotImplementedError(
+                "segment_ids with num_stages > 1: the staged model threads "
+                "one tensor through its stages")
+        return super().forward(ids)
 
 
 class _Stage(nn.Module):
@@ -133,7 +165,7 @@ def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
             if s == num_stages - 1:
                 mods.append(LMHead(H, vocab_size, live_rows_bwd=True))
             stages.append(_Stage(mods))
-    return init_weights(StagedModel(stages))
+    return init_weights(_StagedBert(stages))
 
 
 def synthetic_mlm_batch(batch, seq_len, vocab_size=30528, device="cpu",

@@ -82,24 +82,41 @@ class SelfAttention(nn.Module):
         self.proj = _Linear(hidden, hidden)
         self.dropout = dropout
 
-    def forward(self, x, bias_grad_to_ln=False, seqlens=None):
+    def forward(self, x, bias_grad_to_ln=False, seqlens=None, bounds=None):
         """bias_grad_to_ln: the caller feeds the result straight into a
         FusedLayerNorm and takes (out, lin_bias) — see linear_for_ln.
         seqlens: int32 [B] valid lengths of a right-padded batch (see
         ops/attention.py); the padded rows of the attention output are
-        zero, so the projection returns its bias there."""
-        o = self._attend(x, seqlens)
+        zero, so the projection returns its bias there.
+        bounds: the (kv_lo, kv_hi, q_lo, q_hi) of interval attention
+        (ops/attention.py: packed documents, windows); non-causal only."""
+        o = self._attend(x, seqlens, bounds)
         if bias_grad_to_ln:
             return linear_for_ln(self.proj, o)
         return self.proj(o)
 
-    def _attend(self, x, seqlens=None):
+    def _attend(self, x, seqlens=None, bounds=None):
         from easyparallellibrary_amd.ops.attention import (
-            flash_attention, qkv_flash_attention, qkv_native_ok)
+            flash_attention, interval_attention, qkv_flash_attention,
+            qkv_interval_attention, qkv_native_ok)
         b, s, h = x.shape
         qkv = self.qkv(x).reshape(b, s, 3, self.num_heads, self.head_dim)
         native_here = _NATIVE_ATTN in ("1", "auto")
         p = self.dropout if self.training else 0.0
+        if bounds is not None:
+            if self.causal:
+                raise ValueError("interval bounds need a non-causal "
+                                 "attention (causal: segment_ids / window "
+                                 "of flash_attention)")
+            if native_here and qkv_native_ok(qkv) and not p:
+                o = qkv_interval_attention(qkv, bounds, seqlens=seqlens)
+            else:
+                # dropout has no interval kernel: the torch path, loudly
+                q, k, v = _QKVSplit.apply(qkv)
+                o = interval_attention(q, k, v, bounds, seqlens=seqlens,
+                                       dropout_p=p,
+                                       allow_native=native_here)
+            return o.transpose(1, 2).reshape(b, s, h)
         # dense calls keep the call they always made
         lens = {} if seqlens is None else {"seqlens": seqlens}
         if native_here and qkv_native_ok(qkv):
@@ -160,9 +177,11 @@ class Block(nn.Module):
             return mod(x, bias_grad_to_ln=True, **kwargs)
         return mod(x, **kwargs), None
 
-    def forward(self, x, seqlens=None, x_res=None, pair_out=False):
+    def forward(self, x, seqlens=None, x_res=None, pair_out=False,
+                bounds=None):
         """seqlens: int32 [B] valid lengths of a right-padded batch; only
-        the attention looks at it (every other op is per token).
+        the attention looks at it (every other op is per token).  bounds:
+        interval attention bounds, handed to the attention likewise.
 
         x_res / pair_out (post-LN only) carry a LayerNorm output with two
         consumers across the block boundary as the two tensors of
@@ -181,12 +200,13 @@ class Block(nn.Module):
             # residual add fused into ln2; the summed stream s is the
             # residual carried forward
             a, pb = self._into_ln(self.attn, SelfAttention, self.ln1(x),
-                                  seqlens=seqlens)
+                                  seqlens=seqlens, bounds=bounds)
             y, s = self.ln2.forward_with_sum(a, x, lin_bias=pb)
             return s + self.mlp(y)
         # post-LN: both residual adds fuse into the LN kernels, and the
         # LN backward returns the bias gradient of the Linear before it
-        a, pb = self._into_ln(self.attn, SelfAttention, x, seqlens=seqlens)
+        a, pb = self._into_ln(self.attn, SelfAttention, x, seqlens=seqlens,
+                              bounds=bounds)
         # ln1's output feeds the MLP and ln2's residual
         h, h_res = self.ln1.forward_pair(a, residual=x_res, lin_bias=pb)
         m, fb = self._into_ln(self.mlp, MLP, h)
@@ -204,13 +224,18 @@ class Embeddings(nn.Module):
         nn.init.normal_(self.tok.weight, std=0.02)
         nn.init.normal_(self.pos.weight, std=0.02)
 
-    def forward(self, ids, pair_out=False):
+    def forward(self, ids, pair_out=False, positions=None):
         """pair_out: return the output as the two tensors of
         FusedLayerNorm.forward_pair, for a first block that takes them as
-        (x, x_res)."""
+        (x, x_res).  positions: int [B, S] position of every token
+        (packed documents restart theirs); default 0 .. S-1 along the
+        row."""
         s = ids.shape[1]
-        pos = torch.arange(s, device=ids.device)
-        x = self.tok(ids) + self.pos(pos)[None, :, :]
+        if positions is None:
+            pos = torch.arange(s, device=ids.device)
+            x = self.tok(ids) + self.pos(pos)[None, :, :]
+        else:
+            x = self.tok(ids) + self.pos(positions)
         if pair_out:
             return self.ln.forward_pair(x) if self.ln is not None else (x, x)
         if self.ln is not None:

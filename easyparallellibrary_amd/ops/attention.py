@@ -49,6 +49,36 @@ take the torch path with the same semantics, its boolean mask built from
 the same kv_lo.  ``band_bounds`` computes (kv_lo, q_hi) with torch ops and
 no host sync; a caller with many layers computes them once and passes
 ``bounds=(kv_lo, q_hi)`` instead.
+
+Interval attention (bidirectional packed documents, symmetric windows,
+prefix-LM): ``interval_attention(q, k, v, bounds)`` and, on the packed
+[B, S, 3, H, D] buffer, ``qkv_interval_attention(qkv, bounds)``.  bounds is
+(kv_lo, kv_hi, q_lo, q_hi), four int32 contiguous [B or 1, S] tensors on
+the device of q, each non-decreasing along S.  For sample b with
+len = clamp(seqlens[b], 0, S), query i < len attends key j iff
+
+    kv_lo[b, i] <= j < kv_hi[b, i],   kv_lo[b, i] <= i < kv_hi[b, i] <= len
+
+and (q_lo, q_hi) describe the same mask from the key's side: key j is seen
+by the queries q_lo[b, j] <= i < q_hi[b, j], q_lo[b, j] <= j < q_hi[b, j]
+<= len.  The kernels (csrc/kernels/attention_interval.hip) clamp every
+value where they read it (lower bounds to [0, i], upper to [i + 1, len]),
+so hostile values give a wrong visible set, never a stray access or an
+empty row; nothing is read on the host.  Rows >= len are exact zeros.
+Writing the bounds, with pos = arange(S):
+
+    causal           kv_lo = 0, kv_hi = pos + 1; q_lo = pos, q_hi = S
+                     (flash_attention(causal=True) is the measured path)
+    packed documents interval_bounds(segment_ids, None, S, device):
+                     kv_lo = q_lo = seg_start, kv_hi = q_hi = seg_end
+    window |i-j| < w interval_bounds(None, w, S, device):
+                     kv_lo = q_lo = max(pos - w + 1, 0),
+                     kv_hi = q_hi = min(pos + w, S)
+    prefix-LM, p     kv_lo = 0, kv_hi = max(pos + 1, p);
+                     q_lo = where(pos < p, 0, pos), q_hi = S
+
+No dropout and no dlse: dropout, fp32 and the CPU take the torch path (one
+warning per reason), whose boolean mask comes from kv_lo / kv_hi.
 """
 
 import os
@@ -328,6 +358,112 @@ class _FlashAttentionBand(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
+def interval_bounds(segment_ids, window, seq, device):
+    """(kv_lo, kv_hi, q_lo, q_hi) of the module docstring for packed
+    bidirectional documents and / or a symmetric window |i - j| < window:
+    int32, contiguous, [B, S], or [1, S] when ``segment_ids`` is None.
+    Either argument may be None.  These masks are symmetric, so the query
+    -side bounds are the key-side ones.  torch ops only, no host sync."""
+    lo, hi = band_bounds(segment_ids, window, seq, device)
+    # band_bounds' kv_lo is max(seg_start, i - w + 1) and its q_hi is
+    # min(seg_end, j + w): the two ends of a symmetric interval
+    return lo, hi, lo, hi
+
+
+def _check_interval_bounds(bounds, q):
+    bounds = tuple(bounds)
+    if len(bounds) != 4:
+        raise ValueError("bounds must be (kv_lo, kv_hi, q_lo, q_hi)")
+    for t in bounds:
+        if t.dtype != torch.int32 or t.dim() != 2 \
+                or t.shape[0] not in (1, q.shape[0]) \
+                or t.shape[1] != q.shape[-2] or t.shape != bounds[0].shape:
+            raise ValueError("bounds must be four int32 [B or 1, S] tensors")
+        if t.device != q.device:
+            raise ValueError("bounds must be on the device of q")
+    return tuple(t.contiguous() for t in bounds)
+
+
+def _interval_fwd(q, k, v, scale, bounds, seqlens):
+    b, h, seq, d = q.shape
+    out = torch.empty(b, seq, h, d, dtype=q.dtype,
+                      device=q.device).permute(0, 2, 1, 3)
+    lse = torch.empty(b * h * seq, dtype=torch.float32, device=q.device)
+    native_ext().attn_fwd_interval(q, k, v, out, lse, scale, bounds[0],
+                                   bounds[1], seqlens)
+    return out, lse
+
+
+class _FlashAttentionInterval(torch.autograd.Function):
+    """Interval flash attention: q [B, H, S, D], k / v [B, Hkv, S, D] with
+    Hkv dividing H (MHA included), any kernel-ok strides consumed in place;
+    the four bounds of the module docstring.  Gradients are written in the
+    input layout, dk and dv in the kv shape."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, kv_lo, kv_hi, q_lo, q_hi, seqlens=None):
+        if not _kernel_ok(q):
+            q = q.contiguous()
+        if not (_kernel_ok(k) and _kernel_ok(v)
+                and k.stride() == v.stride()):
+            k, v = k.contiguous(), v.contiguous()
+        out, lse = _interval_fwd(q, k, v, scale, (kv_lo, kv_hi), seqlens)
+        ctx.has_seqlens = seqlens is not None
+        ctx.save_for_backward(q, k, v, out, lse, kv_lo, kv_hi, q_lo, q_hi, *[
+            t for t in (seqlens,) if t is not None])
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
+        q, k, v, out, lse = saved[:5]
+        seqlens = saved[9] if ctx.has_seqlens else None
+        if not _kernel_ok(dout):
+            dout = dout.contiguous()
+        dq = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype,
+                                 device=q.device)
+        dk = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype,
+                                 device=k.device)
+        dv = torch.empty_strided(k.shape, k.stride(), dtype=k.dtype,
+                                 device=k.device)
+        native_ext().attn_bwd_interval(q, k, v, out, dout, lse,
+                                       torch.empty_like(lse), dq, dk, dv,
+                                       ctx.scale, *saved[5:9], seqlens)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+class _QKVFlashAttentionInterval(torch.autograd.Function):
+    """_QKVFlashAttention for interval attention: reads the q / k / v views
+    of the [B, S, 3, H, D] buffer and writes dq / dk / dv into the slices
+    of one d_qkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, scale, kv_lo, kv_hi, q_lo, q_hi, seqlens=None):
+        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
+        out, lse = _interval_fwd(q, k, v, scale, (kv_lo, kv_hi), seqlens)
+        ctx.has_seqlens = seqlens is not None
+        ctx.save_for_backward(qkv, out, lse, kv_lo, kv_hi, q_lo, q_hi, *[
+            t for t in (seqlens,) if t is not None])
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
+        qkv, out, lse = saved[:3]
+        seqlens = saved[7] if ctx.has_seqlens else None
+        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
+        if not _kernel_ok(dout):
+            dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        dq, dk, dv = (dqkv[:, :, i].transpose(1, 2) for i in range(3))
+        native_ext().attn_bwd_interval(q, k, v, out, dout, lse,
+                                       torch.empty_like(lse), dq, dk, dv,
+                                       ctx.scale, *saved[3:7], seqlens)
+        return dqkv, None, None, None, None, None, None
+
+
 class _QKVFlashAttention(torch.autograd.Function):
     """Module-level fused path: consumes the [B,S,3,H,D] qkv projection
     buffer directly.  Forward feeds the kernels the q/k/v strided views
@@ -444,8 +580,10 @@ def flash_attention_with_lse(q, k, v, causal=False, scale=None):
     return out, lse
 
 
-def _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens, kv_lo=None):
-    """The padded-batch (and banded, ``kv_lo`` [B or 1, S]) semantics of
+def _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens, kv_lo=None,
+                 kv_hi=None):
+    """The padded-batch (and banded, ``kv_lo`` [B or 1, S]; interval, with
+    ``kv_hi`` too) semantics of
     the kernels in torch ops (CPU and non-native shapes): a key mask, then
     zeros on the padded query rows.  A padded row keeps its own diagonal
     key (an empty sample: key 0), so its softmax row is finite and the
@@ -464,8 +602,10 @@ def _masked_sdpa(q, k, v, causal, scale, dropout_p, seqlens, kv_lo=None):
     if causal:
         attn_mask = attn_mask & (pos[None, :] <= pos[:, None])
     if kv_lo is not None:
-        attn_mask = (attn_mask & (pos >= kv_lo[:, None, :, None])) \
-            | (pos[None, :] == pos[:, None])
+        attn_mask = attn_mask & (pos >= kv_lo[:, None, :, None])
+        if kv_hi is not None:
+            attn_mask = attn_mask & (pos < kv_hi[:, None, :, None])
+        attn_mask = attn_mask | (pos[None, :] == pos[:, None])
     rows = (pos[None, :] < lens[:, None])[:, None, :, None]    # [B,1,S,1]
     q, k, v = (torch.where(rows, t, torch.zeros_like(t)) for t in (q, k, v))
     out = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask,
@@ -486,6 +626,52 @@ def qkv_flash_attention(qkv, causal=False, scale=None, dropout_p=0.0,
         scale = qkv.shape[-1] ** -0.5
     seqlens = _check_seqlens(seqlens, qkv)
     return _QKVFlashAttention.apply(qkv, causal, scale, dropout_p, seqlens)
+
+
+def interval_attention(q, k, v, bounds, scale=None, seqlens=None,
+                       dropout_p=0.0, allow_native=True):
+    """Interval attention (module docstring).  q: [B, H, S, D]; k, v:
+    [B, Hkv, S, D] with Hkv dividing H; bounds: (kv_lo, kv_hi, q_lo, q_hi),
+    int32 [B or 1, S], from ``interval_bounds`` or written by the caller.
+    Native kernels for bf16 / D = 64 | 128 on the GPU without dropout; the
+    torch path elsewhere, its boolean mask built from kv_lo / kv_hi, with
+    the padded-row semantics of ``seqlens``."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    seqlens = _check_seqlens(seqlens, q)
+    heads, kv_heads = q.shape[1], k.shape[1]
+    if v.shape[1] != kv_heads or kv_heads < 1 or heads % kv_heads:
+        raise ValueError(
+            "k and v must share a head count that divides q's {}, got {} "
+            "and {}".format(heads, kv_heads, v.shape[1]))
+    bounds = _check_interval_bounds(bounds, q)
+    if allow_native and use_native(q):
+        if q.dtype != torch.bfloat16 or q.shape[-1] not in (64, 128):
+            _warn_fallback("dtype={} head_dim={}".format(q.dtype,
+                                                         q.shape[-1]))
+        elif dropout_p:
+            _warn_fallback("interval attention with dropout")
+        else:
+            return _FlashAttentionInterval.apply(q, k, v, scale, *bounds,
+                                                 seqlens)
+    if kv_heads != heads:
+        # autograd sums the expanded gradients over each group
+        k = k.repeat_interleave(heads // kv_heads, dim=1)
+        v = v.repeat_interleave(heads // kv_heads, dim=1)
+    return _masked_sdpa(q, k, v, False, scale, dropout_p, seqlens,
+                        bounds[0], bounds[1])
+
+
+def qkv_interval_attention(qkv, bounds, scale=None, seqlens=None):
+    """``interval_attention`` on the packed [B, S, 3, H, D] projection
+    buffer, as ``qkv_flash_attention``: a [B, H, S, D] view in [B, S, H, D]
+    memory order; the backward writes one d_qkv.  Requires the native
+    kernels (``qkv_native_ok``)."""
+    if scale is None:
+        scale = qkv.shape[-1] ** -0.5
+    seqlens = _check_seqlens(seqlens, qkv)
+    bounds = _check_interval_bounds(bounds, qkv[:, :, 0].transpose(1, 2))
+    return _QKVFlashAttentionInterval.apply(qkv, scale, *bounds, seqlens)
 
 
 def qkv_native_ok(qkv):
@@ -520,7 +706,8 @@ def flash_attention(q, k, v, causal=False, scale=None, allow_native=True,
     if banded:
         if not causal:
             raise ValueError("segment_ids / window need causal=True: a "
-                             "non-causal band is not supported")
+                             "non-causal band is not supported here (see "
+                             "interval_attention)")
         if bounds is None:
             bounds = band_bounds(segment_ids, window, q.shape[-2], q.device)
         bounds = _check_bounds(bounds, q)
