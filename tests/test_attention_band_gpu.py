@@ -12,9 +12,12 @@ phase, one bulk tile and the diagonal, windows of 1 / 32 / 33 / 100 at an
 odd length, and documents + window + seqlens together.  The two samples
 of a batch are segmented differently."""
 
+import functools
+
 import pytest
 import torch
 
+from tests import attn_group_cases as gc
 from tests import kernel_refs as kr
 from tests.test_attention_band_cpu import (
     CUTS_A, CUTS_B, band_valid, doc_ids)
@@ -43,23 +46,22 @@ def band_of(name):
     return seq, ids, window, lens
 
 
-def inputs(family, seq, d, h, hkv):
-    q, _, _, dout = kr.attn_inputs(family, seq, d, True, seed=0, b=B, h=h)
-    _, k, v, _ = kr.attn_inputs(family, seq, d, True, seed=1, b=B, h=hkv)
-    return q, k, v, dout
+@functools.lru_cache(maxsize=None)
+def valid_of(name):
+    """the brute-force [B, 1, S, S] mask of a case; shared, nobody writes
+    into it"""
+    seq, ids, window, lens = band_of(name)
+    return band_valid(ids, window, seq, lens or [seq] * B)
 
 
-def reference(q, k, v, dout, valid):
-    """(ref, bounds) with dk / dv and their bounds summed per group"""
-    b, h, seq, d = q.shape
-    hkv = k.shape[1]
-    ke, ve = (t.repeat_interleave(h // hkv, dim=1) for t in (k, v))
-    ref = kr.attn_ref(q, ke, ve, dout, True, d ** -0.5, valid=valid)
-    bounds = kr.attn_bounds(ref, q, ke, ve, dout, d ** -0.5)
-    for name in ("dk", "dv"):
-        ref[name] = ref[name].view(b, hkv, h // hkv, seq, d).sum(2)
-        bounds[name] = bounds[name].view(b, hkv, h // hkv, seq, d).sum(2)
-    return ref, bounds
+def inputs(family, seq, d, h, hkv, valid=None, lens=None):
+    """the joint families of attn_group_cases.py under the case's mask
+    (None: randn, which needs none)"""
+    assert valid is not None or family == "randn"
+    return gc.group_inputs(family, seq, d, h, hkv, B, valid, lens=lens)
+
+
+reference = gc.group_reference
 
 
 def device_bounds(ids, window, seq):
@@ -121,9 +123,9 @@ def check(got, ref, bounds, lens, tag):
 @pytest.mark.parametrize("d", [64, 128])
 def test_band_against_fp64(d, h, hkv, family, band):
     seq, ids, window, lens = band_of(band)
-    inp = inputs(family, seq, d, h, hkv)
-    ref, bounds = reference(*inp, band_valid(ids, window, seq, lens or
-                                             [seq] * B))
+    valid = valid_of(band)
+    inp = inputs(family, seq, d, h, hkv, valid, lens)
+    ref, bounds = reference(*inp, valid)
     got = run(*inp, *device_bounds(ids, window, seq), lens)
     check(got, ref, bounds, lens, "plain")
 
@@ -143,7 +145,7 @@ def test_band_packed_rope_against_fp64(d, h, hkv, family, band):
     from easyparallellibrary_amd.ops.rope import (
         _rope_torch, rope_qkv_flash_attention, rope_tables)
     seq, ids, window, lens = band_of(band)
-    q, k, v, dout = inputs(family, seq, d, h, hkv)
+    q, k, v, dout = inputs(family, seq, d, h, hkv, valid_of(band), lens)
     flat = torch.cat([t.transpose(1, 2) for t in (q, k, v)], 2).reshape(
         B, seq, (h + 2 * hkv) * d).to(BF16).cuda().requires_grad_()
     buf = flat * 1
@@ -155,8 +157,7 @@ def test_band_packed_rope_against_fp64(d, h, hkv, family, band):
     out.backward(dout.to(BF16).cuda())
     rq, rk, rv = (t.to(F64) for t in buf.detach().cpu().view(
         B, seq, h + 2 * hkv, d).transpose(1, 2).split([h, hkv, hkv], 1))
-    ref, bounds = reference(rq, rk, rv, dout, band_valid(
-        ids, window, seq, lens or [seq] * B))
+    ref, bounds = reference(rq, rk, rv, dout, valid_of(band))
     cos, sin = (t[:seq].to(F64) for t in rope_tables("cpu", d))
     for name in ("dq", "dk"):
         ref[name] = _rope_torch(ref[name], cos, -sin)
@@ -221,7 +222,8 @@ def test_hostile_bounds_stay_inside_the_buffers(d, lo, hi):
 @pytest.mark.parametrize("d,hkv", [(64, 4), (128, 2)])
 def test_band_is_deterministic(d, hkv):
     seq, ids, window, lens = band_of("docs_win70_lens")
-    inp = inputs("peaked", seq, d, 4, hkv)
+    inp = inputs("peaked", seq, d, 4, hkv, valid_of("docs_win70_lens"),
+                 lens)
     bounds = device_bounds(ids, window, seq)
     a, b = run(*inp, *bounds, lens), run(*inp, *bounds, lens)
     for name in a:

@@ -13,6 +13,7 @@ bits: the group sum has one writer and a fixed order.
 import pytest
 import torch
 
+from tests import attn_group_cases as gc
 from tests import kernel_refs as kr
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +24,9 @@ GRADS = ("out", "dq", "dk", "dv")
 
 
 def gqa_inputs(family, seq, d, causal, hkv, b=2, h=6):
-    q, _, _, dout = kr.attn_inputs(family, seq, d, causal, seed=0, b=b, h=h)
-    _, k, v, _ = kr.attn_inputs(family, seq, d, causal, seed=1, b=b, h=hkv)
-    return q, k, v, dout
+    """the joint families of attn_group_cases.py under the dense mask"""
+    return gc.group_inputs(family, seq, d, h, hkv, b,
+                           gc.dense_valid(seq, b, causal))
 
 
 def gqa_ref(q, k, v, dout, causal):

@@ -13,9 +13,12 @@ bulk phase); window 200 (block 1: head, four bulk tiles, tail); windows
 (hidden keys after a row's visible ones); documents + window + seqlens.
 The two samples of a batch are bounded differently."""
 
+import functools
+
 import pytest
 import torch
 
+from tests import attn_group_cases as gc
 from tests import kernel_refs as kr
 from tests.test_attention_band_cpu import CUTS_A, CUTS_B, doc_ids
 from tests.test_attention_interval_cpu import interval_valid
@@ -39,44 +42,53 @@ CASES = {
 PREFIX = (70, 200)
 
 
+def prefix_lm(seq):
+    """(kv_lo, kv_hi, q_lo, q_hi), int64 [B, S], of the prefix-LM case"""
+    pos = torch.arange(seq)
+    p = torch.tensor(PREFIX)[:, None]
+    kv_hi = torch.maximum(pos + 1, p)
+    q_lo = torch.where(pos < p, 0, pos)
+    return (torch.zeros(B, seq, dtype=torch.int64), kv_hi, q_lo,
+            torch.full((B, seq), seq))
+
+
+@functools.lru_cache(maxsize=None)
+def mask_of(name):
+    """(seq, lens, [B, 1, S, S] mask) of a case; needs no GPU.  Shared:
+    nobody writes into the mask"""
+    seq, cuts, window, lens = CASES[name]
+    if name == "prefix_lm":
+        kv_hi = prefix_lm(seq)[1]
+        pos = torch.arange(seq)
+        return seq, lens, (pos[None, None, :] < kv_hi[:, :, None])[:, None]
+    ids = None if cuts is None else torch.stack(
+        [doc_ids(seq, c) for c in cuts])
+    return seq, lens, interval_valid(ids, window, seq, lens or [seq] * B)
+
+
 def case_of(name):
     """(seq, lens, device bounds, [B, 1, S, S] mask) of a case"""
     from easyparallellibrary_amd.ops.attention import interval_bounds
-    seq, cuts, window, lens = CASES[name]
+    seq, lens, valid = mask_of(name)
     if name == "prefix_lm":
-        pos = torch.arange(seq)
-        p = torch.tensor(PREFIX)[:, None]
-        kv_hi = torch.maximum(pos + 1, p)
-        q_lo = torch.where(pos < p, 0, pos)
-        bounds = (torch.zeros(B, seq), kv_hi, q_lo, torch.full((B, seq), seq))
-        bounds = tuple(t.int().contiguous().cuda() for t in bounds)
-        valid = (pos[None, None, :] < kv_hi[:, :, None])[:, None]
+        bounds = tuple(t.int().contiguous().cuda() for t in prefix_lm(seq))
         return seq, lens, bounds, valid
+    _, cuts, window, _ = CASES[name]
     ids = None if cuts is None else torch.stack(
         [doc_ids(seq, c) for c in cuts])
     bounds = interval_bounds(None if ids is None else ids.cuda(), window,
                              seq, "cuda")
-    return seq, lens, bounds, interval_valid(ids, window, seq,
-                                             lens or [seq] * B)
+    return seq, lens, bounds, valid
 
 
-def inputs(family, seq, d, h, hkv):
-    q, _, _, dout = kr.attn_inputs(family, seq, d, False, seed=0, b=B, h=h)
-    _, k, v, _ = kr.attn_inputs(family, seq, d, False, seed=1, b=B, h=hkv)
-    return q, k, v, dout
+def inputs(family, seq, d, h, hkv, valid=None, lens=None):
+    """the joint families of attn_group_cases.py under the case's mask
+    (None: randn, which needs none)"""
+    assert valid is not None or family == "randn"
+    return gc.group_inputs(family, seq, d, h, hkv, B, valid, lens=lens)
 
 
-def reference(q, k, v, dout, valid):
-    """(ref, bounds) with dk / dv and their bounds summed per group"""
-    b, h, seq, d = q.shape
-    hkv = k.shape[1]
-    ke, ve = (t.repeat_interleave(h // hkv, dim=1) for t in (k, v))
-    ref = kr.attn_ref(q, ke, ve, dout, False, d ** -0.5, valid=valid)
-    bounds = kr.attn_bounds(ref, q, ke, ve, dout, d ** -0.5)
-    for name in ("dk", "dv"):
-        ref[name] = ref[name].view(b, hkv, h // hkv, seq, d).sum(2)
-        bounds[name] = bounds[name].view(b, hkv, h // hkv, seq, d).sum(2)
-    return ref, bounds
+reference = gc.group_reference
 
 
 def run(q, k, v, dout, bounds, lens=None):
@@ -132,7 +144,7 @@ def check(got, ref, bounds, lens, tag):
 @pytest.mark.parametrize("d", [64, 128])
 def test_interval_against_fp64(d, h, hkv, family, case):
     seq, lens, bounds, valid = case_of(case)
-    inp = inputs(family, seq, d, h, hkv)
+    inp = inputs(family, seq, d, h, hkv, valid, lens)
     ref, limits = reference(*inp, valid)
     check(run(*inp, bounds, lens), ref, limits, lens, "plain")
 
@@ -144,7 +156,7 @@ def test_qkv_interval_attention_against_fp64(d, family, case):
     """the packed [B, S, 3, H, D] buffer; gradients from the one d_qkv"""
     from easyparallellibrary_amd.ops.attention import qkv_interval_attention
     seq, lens, bounds, valid = case_of(case)
-    q, k, v, dout = inputs(family, seq, d, 4, 4)
+    q, k, v, dout = inputs(family, seq, d, 4, 4, valid, lens)
     ref, limits = reference(q, k, v, dout, valid)
     qkv = torch.stack([t.transpose(1, 2) for t in (q, k, v)], 2).to(
         BF16).cuda().requires_grad_()
@@ -210,8 +222,8 @@ def test_hostile_bounds_stay_inside_the_buffers(d, bad):
 
 @pytest.mark.parametrize("d,hkv", [(64, 4), (128, 2)])
 def test_interval_is_deterministic(d, hkv):
-    seq, lens, bounds, _ = case_of("docs_win70_lens")
-    inp = inputs("peaked", seq, d, 4, hkv)
+    seq, lens, bounds, valid = case_of("docs_win70_lens")
+    inp = inputs("peaked", seq, d, 4, hkv, valid, lens)
     a, b = run(*inp, bounds, lens), run(*inp, bounds, lens)
     for name in a:
         bits = torch.int16 if a[name].dtype == BF16 else torch.int32
