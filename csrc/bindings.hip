@@ -116,6 +116,23 @@ void epl_attn_bwd_interval(const void*, const void*, const void*,
                            const int64_t*, const int64_t*, const int*,
                            const int*, const int*, const int*, const int*,
                            int64_t, hipStream_t);
+void epl_attn_fwd_interval_drop(const void*, const void*, const void*,
+                                void*, float*, int64_t, int64_t, float,
+                                int64_t, int64_t, int64_t, const int64_t*,
+                                const int64_t*, const int64_t*, const int*,
+                                const int*, const int*, int64_t,
+                                unsigned int*, int64_t, unsigned long long,
+                                int, float, hipStream_t);
+void epl_attn_bwd_interval_drop(const void*, const void*, const void*,
+                                const void*, const void*, const float*,
+                                float*, void*, void*, void*, int64_t,
+                                int64_t, float, int64_t, int64_t, int64_t,
+                                const int64_t*, const int64_t*,
+                                const int64_t*, const int64_t*,
+                                const int64_t*, const int64_t*, const int*,
+                                const int*, const int*, const int*,
+                                const int*, int64_t, const unsigned int*,
+                                int64_t, float, hipStream_t);
 void epl_rms_norm_fwd(void*, const void*, const void*, void*, const void*,
                       float*, int64_t, int64_t, float, hipStream_t);
 int64_t epl_rms_norm_bwd_parts(int64_t, int64_t);
@@ -864,10 +881,28 @@ static int64_t attn_interval_bounds(
   return rows;
 }
 
+// the keep-bit tensor of the dropout kernels (attention_interval_drop.hip),
+// int32 [B * H * S * ceil(S / 32)]: metadata only, as attn_fwd checks it
+static unsigned int* attn_interval_mask(const at::Tensor& mask,
+                                        const at::Tensor& q) {
+  check(mask, at::kInt, "mask");
+  const int64_t seq = q.size(2);
+  TORCH_CHECK(mask.numel() == q.size(0) * q.size(1) * seq * ((seq + 31) / 32),
+              "mask size mismatch");
+  TORCH_CHECK(mask.device() == q.device(),
+              "mask must be on the device of q");
+  return reinterpret_cast<unsigned int*>(mask.data_ptr());
+}
+
+// mask / seed / thresh / inv_keep: in-kernel dropout as in attn_fwd (the
+// drop probability is thresh / 256); thresh == 0 or no mask launches the
+// no-dropout kernels
 void attn_fwd_interval(at::Tensor q, at::Tensor k, at::Tensor v,
                        at::Tensor out, at::Tensor lse, double scale,
                        at::Tensor kv_lo, at::Tensor kv_hi,
-                       c10::optional<at::Tensor> seqlens) {
+                       c10::optional<at::Tensor> seqlens,
+                       c10::optional<at::Tensor> mask, int64_t seed,
+                       int64_t thresh, double inv_keep) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 &&
               out.is_cuda() && out.scalar_type() == at::kBFloat16);
   int64_t in_s[3], kv_s[3], o_s[3];
@@ -881,6 +916,18 @@ void attn_fwd_interval(at::Tensor q, at::Tensor k, at::Tensor v,
   const int64_t rows = attn_interval_bounds(
       {{&kv_lo, "kv_lo"}, {&kv_hi, "kv_hi"}}, q);
   if (q.numel() == 0) return;
+  if (mask.has_value() && thresh != 0) {
+    TORCH_CHECK(thresh > 0 && thresh < 256, "thresh range");
+    epl_attn_fwd_interval_drop(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+        lse.data_ptr<float>(), q.size(0) * heads, seq, (float)scale, heads,
+        kv_heads, q.size(3), in_s, kv_s, o_s, attn_seqlens(seqlens, q),
+        kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(), rows == 1 ? 0 : seq,
+        attn_interval_mask(*mask, q), (seq + 31) / 32,
+        (unsigned long long)seed, (int)thresh, (float)inv_keep,
+        cur_stream());
+    return;
+  }
   epl_attn_fwd_interval(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                         out.data_ptr(), lse.data_ptr<float>(),
                         q.size(0) * heads, seq, (float)scale, heads,
@@ -895,7 +942,8 @@ void attn_bwd_interval(at::Tensor q, at::Tensor k, at::Tensor v,
                        at::Tensor delta_ws, at::Tensor dq, at::Tensor dk,
                        at::Tensor dv, double scale, at::Tensor kv_lo,
                        at::Tensor kv_hi, at::Tensor q_lo, at::Tensor q_hi,
-                       c10::optional<at::Tensor> seqlens) {
+                       c10::optional<at::Tensor> seqlens,
+                       c10::optional<at::Tensor> mask, double inv_keep) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
   for (const at::Tensor* t : {&out, &dout, &dq})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16 &&
@@ -918,6 +966,18 @@ void attn_bwd_interval(at::Tensor q, at::Tensor k, at::Tensor v,
       {{&kv_lo, "kv_lo"}, {&kv_hi, "kv_hi"}, {&q_lo, "q_lo"},
        {&q_hi, "q_hi"}}, q);
   if (q.numel() == 0) return;
+  if (mask.has_value()) {
+    epl_attn_bwd_interval_drop(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+        dout.data_ptr(), lse.data_ptr<float>(), delta_ws.data_ptr<float>(),
+        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), q.size(0) * heads, seq,
+        (float)scale, heads, kv_heads, q.size(3), in_s, kv_s, o_s, do_s, g_s,
+        gkv_s, attn_seqlens(seqlens, q), kv_lo.data_ptr<int>(),
+        kv_hi.data_ptr<int>(), q_lo.data_ptr<int>(), q_hi.data_ptr<int>(),
+        rows == 1 ? 0 : seq, attn_interval_mask(*mask, q), (seq + 31) / 32,
+        (float)inv_keep, cur_stream());
+    return;
+  }
   epl_attn_bwd_interval(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                         out.data_ptr(), dout.data_ptr(),
                         lse.data_ptr<float>(), delta_ws.data_ptr<float>(),
@@ -1587,12 +1647,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_interval", &attn_fwd_interval, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("scale"),
         py::arg("kv_lo"), py::arg("kv_hi"),
-        py::arg("seqlens") = py::none());
+        py::arg("seqlens") = py::none(), py::arg("mask") = py::none(),
+        py::arg("seed") = 0, py::arg("thresh") = 0,
+        py::arg("inv_keep") = 1.0);
   m.def("attn_bwd_interval", &attn_bwd_interval, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("out"), py::arg("dout"), py::arg("lse"),
         py::arg("delta_ws"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("scale"), py::arg("kv_lo"), py::arg("kv_hi"),
-        py::arg("q_lo"), py::arg("q_hi"), py::arg("seqlens") = py::none());
+        py::arg("q_lo"), py::arg("q_hi"), py::arg("seqlens") = py::none(),
+        py::arg("mask") = py::none(), py::arg("inv_keep") = 1.0);
   m.def("rms_norm_fwd", &rms_norm_fwd, py::arg("out"), py::arg("x"),
         py::arg("res"), py::arg("s"), py::arg("gamma"), py::arg("rstd"),
         py::arg("eps"));

@@ -108,10 +108,10 @@ class SelfAttention(nn.Module):
                 raise ValueError("interval bounds need a non-causal "
                                  "attention (causal: segment_ids / window "
                                  "of flash_attention)")
-            if native_here and qkv_native_ok(qkv) and not p:
-                o = qkv_interval_attention(qkv, bounds, seqlens=seqlens)
+            if native_here and qkv_native_ok(qkv):
+                o = qkv_interval_attention(qkv, bounds, seqlens=seqlens,
+                                           dropout_p=p)
             else:
-                # dropout has no interval kernel: the torch path, loudly
                 q, k, v = _QKVSplit.apply(qkv)
                 o = interval_attention(q, k, v, bounds, seqlens=seqlens,
                                        dropout_p=p,

@@ -77,8 +77,10 @@ Writing the bounds, with pos = arange(S):
     prefix-LM, p     kv_lo = 0, kv_hi = max(pos + 1, p);
                      q_lo = where(pos < p, 0, pos), q_hi = S
 
-No dropout and no dlse: dropout, fp32 and the CPU take the torch path (one
-warning per reason), whose boolean mask comes from kv_lo / kv_hi.
+dropout_p runs in-kernel (csrc/kernels/attention_interval_drop.hip) with
+the philox keying and the keep-bit tensor of the dense kernels, p quantized
+to 1/256.  No dlse; fp32 and the CPU take the torch path (one warning per
+reason), whose boolean mask comes from kv_lo / kv_hi.
 """
 
 import os
@@ -384,33 +386,41 @@ def _check_interval_bounds(bounds, q):
     return tuple(t.contiguous() for t in bounds)
 
 
-def _interval_fwd(q, k, v, scale, bounds, seqlens):
+def _interval_fwd(q, k, v, scale, bounds, seqlens, dropout_p=0.0):
+    """(out, lse, mask, inv_keep); mask is None without dropout"""
     b, h, seq, d = q.shape
     out = torch.empty(b, seq, h, d, dtype=q.dtype,
                       device=q.device).permute(0, 2, 1, 3)
     lse = torch.empty(b * h * seq, dtype=torch.float32, device=q.device)
+    thresh, inv_keep, seed = _drop_params(dropout_p)
+    mask = _mask_tensor(b, h, seq, q.device) if thresh else None
     native_ext().attn_fwd_interval(q, k, v, out, lse, scale, bounds[0],
-                                   bounds[1], seqlens)
-    return out, lse
+                                   bounds[1], seqlens, mask, seed, thresh,
+                                   inv_keep)
+    return out, lse, mask, inv_keep
 
 
 class _FlashAttentionInterval(torch.autograd.Function):
     """Interval flash attention: q [B, H, S, D], k / v [B, Hkv, S, D] with
     Hkv dividing H (MHA included), any kernel-ok strides consumed in place;
     the four bounds of the module docstring.  Gradients are written in the
-    input layout, dk and dv in the kv shape."""
+    input layout, dk and dv in the kv shape.  dropout_p > 0: the keep
+    bits are drawn in the forward kernel and saved for the backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, kv_lo, kv_hi, q_lo, q_hi, seqlens=None):
+    def forward(ctx, q, k, v, scale, kv_lo, kv_hi, q_lo, q_hi, seqlens=None,
+                dropout_p=0.0):
         if not _kernel_ok(q):
             q = q.contiguous()
         if not (_kernel_ok(k) and _kernel_ok(v)
                 and k.stride() == v.stride()):
             k, v = k.contiguous(), v.contiguous()
-        out, lse = _interval_fwd(q, k, v, scale, (kv_lo, kv_hi), seqlens)
+        out, lse, mask, ctx.inv_keep = _interval_fwd(
+            q, k, v, scale, (kv_lo, kv_hi), seqlens, dropout_p)
+        ctx.has_mask = mask is not None
         ctx.has_seqlens = seqlens is not None
         ctx.save_for_backward(q, k, v, out, lse, kv_lo, kv_hi, q_lo, q_hi, *[
-            t for t in (seqlens,) if t is not None])
+            t for t in (mask, seqlens) if t is not None])
         ctx.scale = scale
         return out
 
@@ -418,7 +428,7 @@ class _FlashAttentionInterval(torch.autograd.Function):
     def backward(ctx, dout):
         saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
         q, k, v, out, lse = saved[:5]
-        seqlens = saved[9] if ctx.has_seqlens else None
+        mask, seqlens = _saved_optionals(ctx, saved[9:])
         if not _kernel_ok(dout):
             dout = dout.contiguous()
         dq = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype,
@@ -429,8 +439,9 @@ class _FlashAttentionInterval(torch.autograd.Function):
                                  device=k.device)
         native_ext().attn_bwd_interval(q, k, v, out, dout, lse,
                                        torch.empty_like(lse), dq, dk, dv,
-                                       ctx.scale, *saved[5:9], seqlens)
-        return dq, dk, dv, None, None, None, None, None, None
+                                       ctx.scale, *saved[5:9], seqlens, mask,
+                                       ctx.inv_keep)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 class _QKVFlashAttentionInterval(torch.autograd.Function):
@@ -439,12 +450,15 @@ class _QKVFlashAttentionInterval(torch.autograd.Function):
     of one d_qkv."""
 
     @staticmethod
-    def forward(ctx, qkv, scale, kv_lo, kv_hi, q_lo, q_hi, seqlens=None):
+    def forward(ctx, qkv, scale, kv_lo, kv_hi, q_lo, q_hi, seqlens=None,
+                dropout_p=0.0):
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
-        out, lse = _interval_fwd(q, k, v, scale, (kv_lo, kv_hi), seqlens)
+        out, lse, mask, ctx.inv_keep = _interval_fwd(
+            q, k, v, scale, (kv_lo, kv_hi), seqlens, dropout_p)
+        ctx.has_mask = mask is not None
         ctx.has_seqlens = seqlens is not None
         ctx.save_for_backward(qkv, out, lse, kv_lo, kv_hi, q_lo, q_hi, *[
-            t for t in (seqlens,) if t is not None])
+            t for t in (mask, seqlens) if t is not None])
         ctx.scale = scale
         return out
 
@@ -452,7 +466,7 @@ class _QKVFlashAttentionInterval(torch.autograd.Function):
     def backward(ctx, dout):
         saved = ctx.saved_tensors  # ONE access: checkpoint unpack hooks
         qkv, out, lse = saved[:3]
-        seqlens = saved[7] if ctx.has_seqlens else None
+        mask, seqlens = _saved_optionals(ctx, saved[7:])
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
         if not _kernel_ok(dout):
             dout = dout.contiguous()
@@ -460,8 +474,9 @@ class _QKVFlashAttentionInterval(torch.autograd.Function):
         dq, dk, dv = (dqkv[:, :, i].transpose(1, 2) for i in range(3))
         native_ext().attn_bwd_interval(q, k, v, out, dout, lse,
                                        torch.empty_like(lse), dq, dk, dv,
-                                       ctx.scale, *saved[3:7], seqlens)
-        return dqkv, None, None, None, None, None, None
+                                       ctx.scale, *saved[3:7], seqlens, mask,
+                                       ctx.inv_keep)
+        return dqkv, None, None, None, None, None, None, None
 
 
 class _QKVFlashAttention(torch.autograd.Function):
@@ -633,9 +648,10 @@ def interval_attention(q, k, v, bounds, scale=None, seqlens=None,
     """Interval attention (module docstring).  q: [B, H, S, D]; k, v:
     [B, Hkv, S, D] with Hkv dividing H; bounds: (kv_lo, kv_hi, q_lo, q_hi),
     int32 [B or 1, S], from ``interval_bounds`` or written by the caller.
-    Native kernels for bf16 / D = 64 | 128 on the GPU without dropout; the
-    torch path elsewhere, its boolean mask built from kv_lo / kv_hi, with
-    the padded-row semantics of ``seqlens``."""
+    Native kernels for bf16 / D = 64 | 128 on the GPU, dropout_p in-kernel
+    (training-mode callers only; p quantized to 1/256); the torch path
+    elsewhere, its boolean mask built from kv_lo / kv_hi, with the
+    padded-row semantics of ``seqlens``."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     seqlens = _check_seqlens(seqlens, q)
@@ -649,11 +665,9 @@ def interval_attention(q, k, v, bounds, scale=None, seqlens=None,
         if q.dtype != torch.bfloat16 or q.shape[-1] not in (64, 128):
             _warn_fallback("dtype={} head_dim={}".format(q.dtype,
                                                          q.shape[-1]))
-        elif dropout_p:
-            _warn_fallback("interval attention with dropout")
         else:
             return _FlashAttentionInterval.apply(q, k, v, scale, *bounds,
-                                                 seqlens)
+                                                 seqlens, dropout_p)
     if kv_heads != heads:
         # autograd sums the expanded gradients over each group
         k = k.repeat_interleave(heads // kv_heads, dim=1)
@@ -662,16 +676,19 @@ def interval_attention(q, k, v, bounds, scale=None, seqlens=None,
                         bounds[0], bounds[1])
 
 
-def qkv_interval_attention(qkv, bounds, scale=None, seqlens=None):
+def qkv_interval_attention(qkv, bounds, scale=None, seqlens=None,
+                           dropout_p=0.0):
     """``interval_attention`` on the packed [B, S, 3, H, D] projection
     buffer, as ``qkv_flash_attention``: a [B, H, S, D] view in [B, S, H, D]
     memory order; the backward writes one d_qkv.  Requires the native
-    kernels (``qkv_native_ok``)."""
+    kernels (``qkv_native_ok``).  dropout_p is applied in-kernel — pass it
+    only in training mode."""
     if scale is None:
         scale = qkv.shape[-1] ** -0.5
     seqlens = _check_seqlens(seqlens, qkv)
     bounds = _check_interval_bounds(bounds, qkv[:, :, 0].transpose(1, 2))
-    return _QKVFlashAttentionInterval.apply(qkv, scale, *bounds, seqlens)
+    return _QKVFlashAttentionInterval.apply(qkv, scale, *bounds, seqlens,
+                                            dropout_p)
 
 
 def qkv_native_ok(qkv):

@@ -29,6 +29,7 @@ ext = CUDAExtension(
         "csrc/kernels/attention_gqa.hip",
         "csrc/kernels/attention_band.hip",
         "csrc/kernels/attention_interval.hip",
+        "csrc/kernels/attention_interval_drop.hip",
     ],
     include_dirs=[os.path.join(ROCM, "include")],
     library_dirs=[os.path.join(ROCM, "lib")],
