@@ -151,6 +151,18 @@ void epl_gather_rows(void*, const void*, const int*, const int*, int64_t,
                      int64_t, int64_t, hipStream_t);
 void epl_scatter_rows_zero(void*, const void*, const int*, int64_t, int64_t,
                            int64_t, hipStream_t);
+void epl_layer_norm_dropout_fwd(void*, const void*, const void*, void*,
+                                const void*, const void*, float*, float*,
+                                int64_t, int64_t, float, uint64_t, int, float,
+                                hipStream_t);
+int64_t epl_layer_norm_dropout_bwd_parts(int64_t);
+void epl_layer_norm_dropout_bwd(void*, void*, void*, void*, void*, int, int,
+                                int, const void*, const void*, const void*,
+                                const void*, const void*, const float*,
+                                const float*, float*, float*, float*, int64_t,
+                                int64_t, uint64_t, int, float, hipStream_t);
+void epl_dropout_add(void*, const void*, const void*, int64_t, int64_t,
+                     uint64_t, int, float, hipStream_t);
 }
 
 namespace {
@@ -420,6 +432,166 @@ void layer_norm_bwd_typed(at::Tensor dx, at::Tensor dgamma, at::Tensor dbeta,
                           c10::optional<at::Tensor> dy2) {
   ln_bwd_fused_impl(dx, dgamma, dbeta, dy, x, gamma, mean, rstd, dadd,
                     colsum_out, dy2, false, "layer_norm_bwd_typed");
+}
+
+// ---- hidden dropout inside the LN kernels (csrc/kernels/ln_dropout.hip) ----
+// Metadata checks only: nothing here reads a value on the host.
+void check_drop(int64_t thresh, double inv_keep, const char* who) {
+  TORCH_CHECK(thresh >= 1 && thresh <= 255, who,
+              ": thresh must be in [1, 255], got ", thresh);
+  TORCH_CHECK(inv_keep >= 1.0, who, ": inv_keep must be >= 1");
+}
+
+// bf16 [.., cols] tensor of x's extent, contiguous, 16-byte aligned
+void check_like(const at::Tensor& t, const at::Tensor& x, const char* name) {
+  check(t, at::kBFloat16, name);
+  TORCH_CHECK(t.numel() == x.numel(), name, " shape mismatch");
+  TORCH_CHECK(t.device() == x.device(), name, " is on another device");
+  check_aligned(t, 16, name);
+}
+
+// s = D(x) (+ res), out = LN(s) * gamma + beta; bf16, cols % 8 == 0,
+// cols <= 4096.  sum_out (s) is always written.
+void layer_norm_dropout_fwd(at::Tensor out, at::Tensor x,
+                            c10::optional<at::Tensor> res, at::Tensor sum_out,
+                            at::Tensor gamma, at::Tensor beta,
+                            at::Tensor mean, at::Tensor rstd, double eps,
+                            int64_t seed, int64_t thresh, double inv_keep) {
+  const char* who = "layer_norm_dropout_fwd";
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, who, ": empty input");
+  const int64_t cols = x.size(-1);
+  const int64_t rows = x.numel() / cols;
+  TORCH_CHECK(cols % 8 == 0 && cols <= 4096, who,
+              ": needs cols % 8 == 0 and cols <= 4096, got ", cols);
+  check_drop(thresh, inv_keep, who);
+  check_like(x, x, "x");
+  check_like(out, x, "out");
+  check_like(sum_out, x, "sum_out");
+  check(gamma, at::kBFloat16, "gamma");
+  check(beta, at::kBFloat16, "beta");
+  check_aligned(gamma, 16, "gamma");
+  check_aligned(beta, 16, "beta");
+  check(mean, at::kFloat, "mean");
+  check(rstd, at::kFloat, "rstd");
+  TORCH_CHECK(gamma.numel() == cols && beta.numel() == cols &&
+              mean.numel() == rows && rstd.numel() == rows,
+              who, ": parameter / statistics shape mismatch");
+  const void* res_p = nullptr;
+  if (res.has_value()) {
+    check_like(*res, x, "res");
+    res_p = res->data_ptr();
+  }
+  epl_layer_norm_dropout_fwd(out.data_ptr(), x.data_ptr(), res_p,
+                             sum_out.data_ptr(), gamma.data_ptr(),
+                             beta.data_ptr(), mean.data_ptr<float>(),
+                             rstd.data_ptr<float>(), rows, cols, (float)eps,
+                             (uint64_t)seed, (int)thresh, (float)inv_keep,
+                             cur_stream());
+}
+
+// The fast LN backward at the saved s, writing d_res = g and
+// d_x = keep ? g * inv_keep : 0; colsum_out is the column sum of d_x.
+// bf16, cols % 8 == 0, cols <= 2048.  dgamma, dbeta, colsum_out: bf16 or
+// fp32, each written in its own dtype.
+void layer_norm_dropout_bwd(at::Tensor d_x, at::Tensor d_res,
+                            at::Tensor dgamma, at::Tensor dbeta,
+                            at::Tensor dy, at::Tensor s, at::Tensor gamma,
+                            at::Tensor mean, at::Tensor rstd,
+                            c10::optional<at::Tensor> dadd,
+                            c10::optional<at::Tensor> colsum_out,
+                            c10::optional<at::Tensor> dy2, int64_t seed,
+                            int64_t thresh, double inv_keep) {
+  const char* who = "layer_norm_dropout_bwd";
+  TORCH_CHECK(s.dim() >= 1 && s.numel() > 0, who, ": empty input");
+  const int64_t cols = s.size(-1);
+  const int64_t rows = s.numel() / cols;
+  TORCH_CHECK(cols % 8 == 0 && cols <= 2048, who,
+              ": needs cols % 8 == 0 and cols <= 2048, got ", cols);
+  check_drop(thresh, inv_keep, who);
+  check_like(s, s, "s");
+  check_like(d_x, s, "d_x");
+  check_like(d_res, s, "d_res");
+  check_like(dy, s, "dy");
+  TORCH_CHECK(d_x.data_ptr() != d_res.data_ptr(), who,
+              ": d_x and d_res must be two tensors");
+  check(gamma, at::kBFloat16, "gamma");
+  check_aligned(gamma, 16, "gamma");
+  check(mean, at::kFloat, "mean");
+  check(rstd, at::kFloat, "rstd");
+  const int mode_g = store_mode(dgamma, "dgamma");
+  const int mode_b = store_mode(dbeta, "dbeta");
+  TORCH_CHECK(gamma.numel() == cols && dgamma.numel() == cols &&
+              dbeta.numel() == cols && mean.numel() == rows &&
+              rstd.numel() == rows,
+              who, ": parameter / statistics shape mismatch");
+  const void* dadd_p = nullptr;
+  const void* dy2_p = nullptr;
+  void* cs_out = nullptr;
+  int mode_c = 1;
+  if (dadd.has_value()) {
+    check_like(*dadd, s, "dadd");
+    dadd_p = dadd->data_ptr();
+  }
+  if (dy2.has_value()) {
+    check_like(*dy2, s, "dy2");
+    dy2_p = dy2->data_ptr();
+  }
+  if (colsum_out.has_value()) {
+    mode_c = store_mode(*colsum_out, "colsum_out");
+    TORCH_CHECK(colsum_out->numel() == cols, "colsum_out shape mismatch");
+    cs_out = colsum_out->data_ptr();
+  }
+  const int64_t nparts = epl_layer_norm_dropout_bwd_parts(rows);
+  at::Tensor ws = at::empty({cs_out ? 3 : 2, nparts, cols},
+                            s.options().dtype(at::kFloat));
+  float* dgp = ws.data_ptr<float>();
+  float* dbp = dgp + nparts * cols;
+  float* csp = cs_out ? dbp + nparts * cols : nullptr;
+  epl_layer_norm_dropout_bwd(
+      d_x.data_ptr(), d_res.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+      cs_out, mode_g == 2, mode_b == 2, mode_c == 2, dy.data_ptr(), dy2_p,
+      s.data_ptr(), gamma.data_ptr(), dadd_p, mean.data_ptr<float>(),
+      rstd.data_ptr<float>(), dgp, dbp, csp, rows, cols, (uint64_t)seed,
+      (int)thresh, (float)inv_keep, cur_stream());
+}
+
+static void dropout_add_extents(const at::Tensor& x, int64_t* rows,
+                                int64_t* cols) {
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "dropout_add: empty input");
+  *cols = x.size(-1);
+  *rows = x.numel() / *cols;
+  TORCH_CHECK(*cols % 8 == 0, "dropout_add: cols must be a multiple of 8");
+  TORCH_CHECK(*cols <= (int64_t(1) << 24), "dropout_add: cols too large");
+}
+
+// out = D(x) (+ res): bf16 [.., cols], cols % 8 == 0
+void dropout_add_fwd(at::Tensor out, at::Tensor x,
+                     c10::optional<at::Tensor> res, int64_t seed,
+                     int64_t thresh, double inv_keep) {
+  int64_t rows, cols;
+  dropout_add_extents(x, &rows, &cols);
+  check_drop(thresh, inv_keep, "dropout_add_fwd");
+  check_like(x, x, "x");
+  check_like(out, x, "out");
+  const void* res_p = nullptr;
+  if (res.has_value()) {
+    check_like(*res, x, "res");
+    res_p = res->data_ptr();
+  }
+  epl_dropout_add(out.data_ptr(), x.data_ptr(), res_p, rows, cols,
+                  (uint64_t)seed, (int)thresh, (float)inv_keep, cur_stream());
+}
+
+// dx = keep ? g * inv_keep : 0 with the forward's keep
+void dropout_add_bwd(at::Tensor dx, at::Tensor g, int64_t seed,
+                     int64_t thresh, double inv_keep) {
+  int64_t rows, cols;
+  dropout_add_extents(g, &rows, &cols);
+  check_drop(thresh, inv_keep, "dropout_add_bwd");
+  check_like(g, g, "g");
+  check_like(dx, g, "dx");
+  epl_dropout_add(dx.data_ptr(), g.data_ptr(), nullptr, rows, cols,
+                  (uint64_t)seed, (int)thresh, (float)inv_keep, cur_stream());
 }
 
 void bias_gelu_fwd(at::Tensor out, at::Tensor x, at::Tensor bias) {
@@ -1584,6 +1756,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("dadd") = py::none(), py::arg("colsum_out") = py::none(),
         py::arg("dy2") = py::none());
+  m.def("layer_norm_dropout_fwd", &layer_norm_dropout_fwd);
+  m.def("layer_norm_dropout_bwd", &layer_norm_dropout_bwd, py::arg("d_x"),
+        py::arg("d_res"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dy"),
+        py::arg("s"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
+        py::arg("dadd"), py::arg("colsum_out"), py::arg("dy2"),
+        py::arg("seed"), py::arg("thresh"), py::arg("inv_keep"));
+  m.def("dropout_add_fwd", &dropout_add_fwd);
+  m.def("dropout_add_bwd", &dropout_add_bwd);
   m.def("bias_gelu_fwd", &bias_gelu_fwd);
   m.def("bias_gelu_bwd", &bias_gelu_bwd);
   m.def("bias_gelu_bwd_typed", &bias_gelu_bwd_typed);

@@ -46,13 +46,15 @@ class BertCore(nn.Module):
     ignores most positions)."""
 
     def __init__(self, layers, hidden, heads, ffn, vocab_size, max_pos,
-                 dropout=0.0, pad_token_id=None, live_rows_bwd=False):
+                 dropout=0.0, pad_token_id=None, live_rows_bwd=False,
+                 hidden_dropout=0.0):
         super().__init__()
         self.pad_token_id = pad_token_id
-        self.embeddings = Embeddings(vocab_size, hidden, max_pos)
+        self.embeddings = Embeddings(vocab_size, hidden, max_pos,
+                                     dropout=hidden_dropout)
         self.blocks = nn.ModuleList(
             Block(hidden, heads, ffn, causal=False, pre_ln=False,
-                  dropout=dropout)
+                  dropout=dropout, hidden_dropout=hidden_dropout)
             for _ in range(layers))
         self.head = LMHead(hidden, vocab_size, live_rows_bwd=live_rows_bwd)
 
@@ -132,9 +134,12 @@ class _Stage(nn.Module):
 
 
 def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
-               num_stages=1, dropout=0.0, pad_token_id=None):
+               num_stages=1, dropout=0.0, pad_token_id=None,
+               hidden_dropout=0.0):
     """Build BERT under epl annotations.  vocab defaults to 30528
     (30522 rounded up to /8 for the fused CE kernel's vectorized path).
+    dropout: attention dropout; hidden_dropout: dropout of the hidden
+    stream (models/transformer.py).
     pad_token_id: train on right-padded batches (see BertCore); single
     stage only."""
     cfg = BERT_CONFIGS[config] if isinstance(config, str) else dict(config)
@@ -143,7 +148,8 @@ def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
         with epl.replicate(device_count=1, name="stage_0"):
             model = BertCore(L, H, A, F, vocab_size, max_pos,
                              dropout=dropout, pad_token_id=pad_token_id,
-                             live_rows_bwd=True)
+                             live_rows_bwd=True,
+                             hidden_dropout=hidden_dropout)
         return init_weights(model)
     if pad_token_id is not None:
         raise ValueError(
@@ -157,9 +163,11 @@ def build_bert(config="bert-large", vocab_size=30528, max_pos=512,
         with epl.replicate(device_count=1, name="stage_{}".format(s)):
             mods = []
             if s == 0:
-                mods.append(Embeddings(vocab_size, H, max_pos))
+                mods.append(Embeddings(vocab_size, H, max_pos,
+                                       dropout=hidden_dropout))
             n = min(per, L - layer_idx)
-            mods.extend(Block(H, A, F, dropout=dropout)
+            mods.extend(Block(H, A, F, dropout=dropout,
+                              hidden_dropout=hidden_dropout)
                         for _ in range(n))
             layer_idx += n
             if s == num_stages - 1:

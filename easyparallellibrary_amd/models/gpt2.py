@@ -20,13 +20,13 @@ GPT2_CONFIGS = {
 
 class GPT2Core(nn.Module):
     def __init__(self, layers, hidden, heads, ffn, vocab_size, max_pos,
-                 dropout=0.0):
+                 dropout=0.0, hidden_dropout=0.0):
         super().__init__()
         self.embeddings = Embeddings(vocab_size, hidden, max_pos,
-                                     use_ln=False)
+                                     use_ln=False, dropout=hidden_dropout)
         self.blocks = nn.ModuleList(
             Block(hidden, heads, ffn, causal=True, pre_ln=True,
-                  dropout=dropout)
+                  dropout=dropout, hidden_dropout=hidden_dropout)
             for _ in range(layers))
         self.head = LMHead(hidden, vocab_size, use_ln=True)
 
@@ -38,14 +38,16 @@ class GPT2Core(nn.Module):
 
 
 def build_gpt2(config="gpt2-xl", vocab_size=50264, max_pos=1024,
-               num_stages=1, dropout=0.0):
-    """vocab 50257 rounded up to /8 for the vectorized CE kernel."""
+               num_stages=1, dropout=0.0, hidden_dropout=0.0):
+    """vocab 50257 rounded up to /8 for the vectorized CE kernel.
+    dropout: attention dropout; hidden_dropout: dropout of the hidden
+    stream (models/transformer.py)."""
     cfg = GPT2_CONFIGS[config] if isinstance(config, str) else dict(config)
     L, H, A, F = cfg["layers"], cfg["hidden"], cfg["heads"], cfg["ffn"]
     if num_stages <= 1:
         with epl.replicate(device_count=1, name="stage_0"):
             model = GPT2Core(L, H, A, F, vocab_size, max_pos,
-                             dropout=dropout)
+                             dropout=dropout, hidden_dropout=hidden_dropout)
         return init_weights(model)
     per = (L + num_stages - 1) // num_stages
     stages = []
@@ -54,10 +56,12 @@ def build_gpt2(config="gpt2-xl", vocab_size=50264, max_pos=1024,
         with epl.replicate(device_count=1, name="stage_{}".format(s)):
             mods = []
             if s == 0:
-                mods.append(Embeddings(vocab_size, H, max_pos, use_ln=False))
+                mods.append(Embeddings(vocab_size, H, max_pos, use_ln=False,
+                                       dropout=hidden_dropout))
             n = min(per, L - layer_idx)
             mods.extend(Block(H, A, F, causal=True, pre_ln=True,
-                              dropout=dropout)
+                              dropout=dropout,
+                              hidden_dropout=hidden_dropout)
                         for _ in range(n))
             layer_idx += n
             if s == num_stages - 1:

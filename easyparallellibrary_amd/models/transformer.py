@@ -6,6 +6,15 @@ Hot ops ride the hand-written CDNA4 kernels: FusedLayerNorm,
 FusedBiasGelu (FFN first Linear runs bias-free), and the fused-qkv flash
 attention — DEFAULT for causal and non-causal, with in-kernel philox
 dropout (see _NATIVE_ATTN below).
+
+Dropout comes in the two halves of the BERT / GPT-2 recipes.  ``dropout``
+is the attention-probability dropout, inside the attention kernels.
+``hidden_dropout`` (Block) and ``dropout`` (Embeddings) drop the hidden
+stream: the output of the attention projection and of fc2, each before
+its residual add, and the embeddings.  Where a FusedLayerNorm takes the
+sum (both sites of a post-LN block, ln2 of a pre-LN block) the drop runs
+inside the LN kernels; the pre-LN tail and the embeddings use
+ops.layer_norm.dropout_add.  Every default is 0.
 """
 
 import os
@@ -26,6 +35,7 @@ _NATIVE_ATTN = os.environ.get("EPL_NATIVE_ATTENTION", "auto")
 from easyparallellibrary_amd.ops.bias_gelu import FusedBiasGelu
 from easyparallellibrary_amd.ops.bias_linear import FusedBiasLinear
 from easyparallellibrary_amd.ops.layer_norm import (FusedLayerNorm,
+                                                    dropout_add,
                                                     linear_for_ln)
 from easyparallellibrary_amd.ops.lm_head import (LiveRowsLinear,
                                                  resolve_live_rows)
@@ -155,12 +165,15 @@ class MLP(nn.Module):
 
 
 class Block(nn.Module):
-    """Transformer block; pre_ln=True for GPT-style, False for BERT."""
+    """Transformer block; pre_ln=True for GPT-style, False for BERT.
+    dropout: attention dropout.  hidden_dropout: dropout of the attention
+    projection's and of fc2's output before their residual adds."""
 
     def __init__(self, hidden, num_heads, ffn_hidden, causal=False,
-                 pre_ln=False, dropout=0.0):
+                 pre_ln=False, dropout=0.0, hidden_dropout=0.0):
         super().__init__()
         self.pre_ln = pre_ln
+        self.hidden_dropout = hidden_dropout
         self.ln1 = FusedLayerNorm(hidden)
         self.attn = SelfAttention(hidden, num_heads, causal=causal,
                                   dropout=dropout)
@@ -194,6 +207,9 @@ class Block(nn.Module):
         tensor is used twice and autograd adds the gradients."""
         if x_res is None:
             x_res = x
+        # the LN calls stay the ones they were unless hidden dropout is on
+        hd = self.hidden_dropout if self.training else 0.0
+        drop = {"dropout_p": hd} if hd else {}
         if self.pre_ln:
             if pair_out or x_res is not x:
                 raise ValueError("x_res / pair_out are post-LN only")
@@ -201,23 +217,31 @@ class Block(nn.Module):
             # residual carried forward
             a, pb = self._into_ln(self.attn, SelfAttention, self.ln1(x),
                                   seqlens=seqlens, bounds=bounds)
-            y, s = self.ln2.forward_with_sum(a, x, lin_bias=pb)
+            y, s = self.ln2.forward_with_sum(a, x, lin_bias=pb, **drop)
+            if hd:
+                return dropout_add(self.mlp(y), s, hd)
             return s + self.mlp(y)
         # post-LN: both residual adds fuse into the LN kernels, and the
         # LN backward returns the bias gradient of the Linear before it
         a, pb = self._into_ln(self.attn, SelfAttention, x, seqlens=seqlens,
                               bounds=bounds)
         # ln1's output feeds the MLP and ln2's residual
-        h, h_res = self.ln1.forward_pair(a, residual=x_res, lin_bias=pb)
+        h, h_res = self.ln1.forward_pair(a, residual=x_res, lin_bias=pb,
+                                         **drop)
         m, fb = self._into_ln(self.mlp, MLP, h)
         if pair_out:
-            return self.ln2.forward_pair(m, residual=h_res, lin_bias=fb)
-        return self.ln2(m, residual=h_res, lin_bias=fb)
+            return self.ln2.forward_pair(m, residual=h_res, lin_bias=fb,
+                                         **drop)
+        return self.ln2(m, residual=h_res, lin_bias=fb, **drop)
 
 
 class Embeddings(nn.Module):
-    def __init__(self, vocab_size, hidden, max_positions, use_ln=True):
+    """dropout: hidden dropout of the output (after the LayerNorm)."""
+
+    def __init__(self, vocab_size, hidden, max_positions, use_ln=True,
+                 dropout=0.0):
         super().__init__()
+        self.dropout = dropout
         self.tok = nn.Embedding(vocab_size, hidden)
         self.pos = nn.Embedding(max_positions, hidden)
         self.ln = FusedLayerNorm(hidden) if use_ln else None
@@ -236,6 +260,11 @@ class Embeddings(nn.Module):
             x = self.tok(ids) + self.pos(pos)[None, :, :]
         else:
             x = self.tok(ids) + self.pos(positions)
+        if self.dropout and self.training:
+            if self.ln is not None:
+                x = self.ln(x)
+            x = dropout_add(x, None, self.dropout)
+            return (x, x) if pair_out else x
         if pair_out:
             return self.ln.forward_pair(x) if self.ln is not None else (x, x)
         if self.ln is not None:

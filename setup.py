@@ -21,6 +21,7 @@ ext = CUDAExtension(
         "csrc/comm/rccl_comm.hip",
         "csrc/kernels/kernels.hip",
         "csrc/kernels/llama_ops.hip",
+        "csrc/kernels/ln_dropout.hip",
         "csrc/kernels/moe.hip",
         "csrc/kernels/moe_router.hip",
         "csrc/kernels/moe_gemm.hip",
